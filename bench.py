@@ -2,6 +2,20 @@
 """bench.py -- FA2 forward+backward on MI355X, BASELINE.json's headline metric.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c5|c1]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs when
+--dump-outputs is given and prints the result line (metric, value, unit, ms_per_step,
+...).  Everything else this file measures -- the per-launch roofline region, the other
+configs (extra_configs), the CPU baselines -- takes runs of its own and is behind
+--full; without it those entries of the line are null.
+
+--dump-outputs DIR writes what the timed path computed in its last timed step, the
+arrays its caller receives (O, LSE, dQ, dK, dV of this rank), as DIR/<name>.npy in
+float32 (DIR/<name>.rank<r>.npy on ranks r > 0).  An array above DUMP_MAX_ELEMS
+elements is stored as a fixed sample of its flattened elements (dump_indices: seeded,
+the same for every run and build), so a dump stays below 64 MB.  The inputs are seeded,
+so two builds run with the same arguments are compared output for output.
 
 One *step* = the FA2 forward (O, LSE) + backward (dQ, dK, dV; fa2_backward's launch
 plan) over one batch of synthetic fp32 inputs already resident in HBM (harness
@@ -15,12 +29,14 @@ Workloads (BASELINE.json configs):
     north star's 1/2/4/8-GPU curve: every rank takes the contiguous B*H slice
     fa2_shard_range gives it (one process per GPU, no data-path collective;
     RCCL only carries the timing barrier and the max over ranks).  The N = 1 line
-    also times C5 on one GPU (extra_configs.c5_1gpu) as the curve's anchor.
+    of a --full run also times C5 on one GPU (extra_configs.c5_1gpu) as the curve's
+    anchor.
 `--gpus N` without a launcher starts N ranks itself (torch.distributed.run, before
 any GPU call in this process) and exits with their status.
 
 value = algorithmic fwd+bwd FLOPs of the job (14*B*H*S^2*D) / the max over ranks of
 the K-step wall time (barrier + synchronize on both sides).
+With --full:
 roofline = the dominant kernel launch's algorithmic FLOPs / its mean duration, timed
 live with HIP events on the launch's own stream around every launch of a second
 K-step region, against the dense fp16 MFMA peak; step_frac = the whole step's
@@ -64,6 +80,34 @@ METRIC = "FA2 fwd+bwd TFLOPS & HBM GB/s (% of gfx950 roofline) at S=2048 D=64"
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+# --dump-outputs: at most this many elements of one array (5 arrays x 8 MB of float32)
+DUMP_MAX_ELEMS = 2 * 1024 * 1024
+
+
+def dump_indices(name: str, n: int):
+    """The flattened elements of an n-element output `name` that a dump holds: all of them
+    (None) up to DUMP_MAX_ELEMS, else DUMP_MAX_ELEMS sorted indices drawn (with
+    replacement) from a generator seeded by the name and n alone."""
+    if n <= DUMP_MAX_ELEMS:
+        return None
+    seed = [n] + [ord(c) for c in name]
+    return np.sort(np.random.default_rng(seed).integers(0, n, size=DUMP_MAX_ELEMS, dtype=np.int64))
+
+
+def dump_outputs(torch, out_dir: str, rank: int, arrays: dict):
+    """Write the device tensors `arrays` as float32 out_dir/<name>.npy (see the module
+    docstring); the caller has synchronised the device."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        idx = dump_indices(name, flat.numel())
+        if idx is not None:
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        a = flat.to(torch.float32).cpu().numpy()
+        a = a if idx is not None else a.reshape(tuple(t.shape))
+        np.save(os.path.join(out_dir, f"{name}.npy" if rank == 0 else f"{name}.rank{rank}.npy"), a)
 
 
 # kernel-name prefixes in the rocprofv3 PMC summary
@@ -366,8 +410,15 @@ def main():
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default=None,
                     help="default: c3 on one GPU, c5 (strong-scaled) on more")
     ap.add_argument("--precision", choices=["fp16", "fp32", "bf16"], default="fp16")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the S sweep / C2 / C4 / C5 extra configs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's O, LSE, dQ, dK, dV as DIR/<name>.npy "
+                         "(float32; a fixed seeded sample of arrays above DUMP_MAX_ELEMS elements)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the per-launch roofline region, "
+                         "the extra configs and the CPU baselines")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the S sweep / C2 / C4 / C5 extra configs")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher and rank plumbing only (gloo, no GPU work): the JSON line without numbers")
     args = ap.parse_args()
@@ -472,7 +523,6 @@ def main():
         if warm_steps >= args.warmup:
             torch.cuda.synchronize(dev)
     torch.cuda.synchronize(dev)
-    events = [[torch.cuda.Event(enable_timing=True) for _ in range(len(kernels) + 1)] for _ in range(args.steps)]
 
     # timed region 1 -> value: K steps exactly as a caller issues them (no event between
     # kernels: a timing event serialises the stream)
@@ -488,16 +538,9 @@ def main():
         dist.barrier()
         elapsed = all_max(torch, dist, dev, elapsed)
 
-    # timed region 2 -> roofline: the same K steps with HIP events around every launch
-    # on its stream (the isolated per-launch durations rocprofv3's kernel trace reports)
-    torch.cuda.synchronize(dev)
-    t1 = time.perf_counter()
-    for s in range(args.steps):
-        step(events[s])
-    torch.cuda.synchronize(dev)
-    elapsed_ev = time.perf_counter() - t1
-    kms = {name: float(np.mean([events[s][i].elapsed_time(events[s][i + 1]) for s in range(args.steps)]))
-           for i, name in enumerate(kernels)}
+    # what the last timed step left in the caller's buffers, before anything else runs
+    if args.dump_outputs:
+        dump_outputs(torch, args.dump_outputs, rank, {"o": o, "lse": lse, "dq": dq, "dk": dk, "dv": dv})
 
     per_head = S * S * D
     flops = 14.0 * per_head * total_heads * args.steps
@@ -505,28 +548,43 @@ def main():
     hbm_bytes = (48.0 * S * D + 8.0 * S) * total_heads * args.steps  # fwd 16SD+4S, bwd 32SD+4S per head
     ms_per_step = elapsed / args.steps * 1e3
 
-    # dominant launch and its algorithmic FLOPs per head: fwd 4 S^2 D; dK/dV 8 S^2 D (S,
-    # dP, dV, dK: four of the backward's five GEMMs); dQ 2 S^2 D (its S and dP recompute
-    # earns nothing); a whole backward 10 S^2 D
-    alg = {"fwd": 4.0, "dq": 2.0, "dkdv": 8.0, "bwd": 10.0}
-    dom = max(kms, key=kms.get)
-    dom_flops = alg[dom] * per_head * heads
-    peak = MFMA_F16_PEAK_TFLOPS if prec in ("fp16", "bf16") else MFMA_F32_PEAK_TFLOPS
-    achieved = dom_flops / (kms[dom] * 1e-3) / 1e12
-    traffic = traffic_from_profile(dom if prec != "fp32" else "bwd32", D, S, heads, fa2amd.build_id())
-    roof = {"bound": "mfma", "kernel": dom, "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s",
-            "frac": round(achieved / peak, 4), "traffic": traffic,
-            # the whole step against the same peak: 14 S^2 D per head per step / ms_per_step
-            "step_frac": round(tflops / peak, 4),
-            "kernel_ms": {n: round(x, 4) for n, x in kms.items()},
-            "bwd_tflops": round(10.0 * per_head * heads / (sum(kms[n] for n in kms if n != "fwd") * 1e-3) / 1e12, 2),
-            "ms_per_step_with_events": round(elapsed_ev / args.steps * 1e3, 4)}
+    roof = None
+    if args.full:
+        # timed region 2 -> roofline: the same K steps with HIP events around every launch
+        # on its stream (the isolated per-launch durations rocprofv3's kernel trace reports)
+        events = [[torch.cuda.Event(enable_timing=True) for _ in range(len(kernels) + 1)] for _ in range(args.steps)]
+        torch.cuda.synchronize(dev)
+        t1 = time.perf_counter()
+        for s in range(args.steps):
+            step(events[s])
+        torch.cuda.synchronize(dev)
+        elapsed_ev = time.perf_counter() - t1
+        kms = {name: float(np.mean([events[s][i].elapsed_time(events[s][i + 1]) for s in range(args.steps)]))
+               for i, name in enumerate(kernels)}
+
+        # dominant launch and its algorithmic FLOPs per head: fwd 4 S^2 D; dK/dV 8 S^2 D (S,
+        # dP, dV, dK: four of the backward's five GEMMs); dQ 2 S^2 D (its S and dP recompute
+        # earns nothing); a whole backward 10 S^2 D
+        alg = {"fwd": 4.0, "dq": 2.0, "dkdv": 8.0, "bwd": 10.0}
+        dom = max(kms, key=kms.get)
+        dom_flops = alg[dom] * per_head * heads
+        peak = MFMA_F16_PEAK_TFLOPS if prec in ("fp16", "bf16") else MFMA_F32_PEAK_TFLOPS
+        achieved = dom_flops / (kms[dom] * 1e-3) / 1e12
+        traffic = traffic_from_profile(dom if prec != "fp32" else "bwd32", D, S, heads, fa2amd.build_id())
+        roof = {"bound": "mfma", "kernel": dom, "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s",
+                "frac": round(achieved / peak, 4), "traffic": traffic,
+                # the whole step against the same peak: 14 S^2 D per head per step / ms_per_step
+                "step_frac": round(tflops / peak, 4),
+                "kernel_ms": {n: round(x, 4) for n, x in kms.items()},
+                "bwd_tflops": round(10.0 * per_head * heads / (sum(kms[n] for n in kms if n != "fwd") * 1e-3) / 1e12,
+                                    2),
+                "ms_per_step_with_events": round(elapsed_ev / args.steps * 1e3, 4)}
 
     cpu = None
     extra = None
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         extra = extras(fa2amd, torch, dev)
-    elif world > 1 and not args.no_extras:
+    elif args.full and world > 1 and not args.no_extras:
         extra = {f"sweep_B2_H8_D64_fp16_fwdbwd_sharded{world}": sweep_sharded(fa2amd, torch, dev, dist, world, rank)}
         # the reference's host-buffer semantics at the N-GPU point: rank 0 shards C5 over
         # all N devices through fa2_*_host (one host thread per device) while the other
@@ -545,7 +603,7 @@ def main():
                 log("c5 host-API entry failed:", e)
                 extra["c5_host_api_pcie_inclusive"] = None
         dist.barrier()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             cpu = cpu_baseline(S, D, 16)
         except Exception as e:  # the baseline is reported, never required
@@ -561,6 +619,7 @@ def main():
             "warmup": args.warmup,
             "warmup_steps_run": warm_steps,
             "ms_per_step": round(ms_per_step, 4),
+            "full": args.full,
             "higher_is_better": True,
             "scaling": "weak" if per_rank else "strong",
             "vs_baseline": None,

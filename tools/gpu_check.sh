@@ -21,8 +21,8 @@ for s in $STEPS; do
   case $s in
     smoke)  run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
     pytest) run pytest_gpu 1200 python -m pytest tests -m gpu -q --timeout 300 -p no:cacheprovider ${PYTEST_ARGS} ;;
-    bench)  run bench 600 python bench.py ${BENCH_ARGS} ;;
-    prof)   run prof 600 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run --output-format csv -- python3 bench.py --no-cpu-baseline --no-extras --steps 50 --warmup 20 ;;
+    bench)  run bench 600 python bench.py --full ${BENCH_ARGS} ;;
+    prof)   run prof 600 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run --output-format csv -- python3 bench.py --full --no-cpu-baseline --no-extras --steps 50 --warmup 20 ;;
   esac
 done
 echo done >> $OUT/status.txt
