@@ -67,7 +67,7 @@ std::atomic<int> g_tune_n{0};
 const char* const kKnobs[] = {"FWD_HS",   "FWD_WAVES", "FWD_KS",          "FWD_NKB", "DKDV_WAVES", "DKDV_QS",
                               "DKDV_HS",  "DQ_WAVES",  "DQ_KS",           "DQ_HS",   "BWD_FUSED",  "BWD_FUSED_DELTA",
                               "BWD_FQS",  "BWD_FKS",   "BWD_FNW",         "HOST_SHARDS_ON_DEVICE0",    "HOST_CHUNKS",
-                              "FWD_SPLIT", "BWD_SPLIT"};
+                              "FWD_SPLIT", "BWD_SPLIT", "BWD_CAUSAL_PART"};
 bool known_knob(const char* k) {
     for (const char* n : kKnobs)
         if (!strcmp(n, k)) return true;
@@ -167,6 +167,24 @@ void stream_scratch_release() {
     if (have) (void)hipSetDevice(dev0);
 }
 
+const char* causal_override(bool fwd, bool bwd) {
+    if (g_tune_n.load(std::memory_order_acquire) == 0) return nullptr;
+    if (fwd) {
+        if (tune_knob("FWD_HS", -1) == 1) return "FWD_HS";
+        if (tune_knob("FWD_SPLIT", 0) >= 2) return "FWD_SPLIT";
+        for (const char* n : {"FWD_KS", "FWD_WAVES", "FWD_NKB"})
+            if (tune_knob(n, 0)) return n;
+    }
+    if (bwd) {
+        for (const char* n : {"DQ_HS", "DKDV_HS", "BWD_FUSED"})
+            if (tune_knob(n, -1) == 1) return n;
+        if (tune_knob("BWD_SPLIT", 0) >= 2) return "BWD_SPLIT";
+        for (const char* n : {"DQ_KS", "DQ_WAVES", "DKDV_QS", "DKDV_WAVES"})
+            if (tune_knob(n, 0)) return n;
+    }
+    return nullptr;
+}
+
 int auto_waves(long blocks32, int maxnw, int minnw) {
     const int ncu = cu_count();
     for (int nw = maxnw; nw > minnw; nw /= 2)
@@ -259,6 +277,60 @@ int fa2_backward(const float* q, const float* k, const float* v, const float* o,
         : precision == FA2_BF16 ? fa2::launch_backward_bf16(D, q, k, v, o, dout, lse, delta, dq, dk, dv, B * H, S, st)
                                 : fa2::launch_backward_f32(D, q, k, v, o, dout, lse, delta, dq, dk, dv, B * H, S, st);
     return hip_status(e, "fa2_backward launch");
+}
+
+}  // extern "C"
+
+namespace {
+// mask and precision of the *_masked entry points (before any HIP call)
+int check_mask(int mask, int precision) {
+    if (mask != FA2_MASK_NONE && mask != FA2_MASK_CAUSAL)
+        return fail(FA2_E_INVALID, "mask must be FA2_MASK_NONE or FA2_MASK_CAUSAL");
+    if (mask == FA2_MASK_CAUSAL && precision == FA2_FP32)
+        return fail(FA2_E_INVALID, "the causal mask needs FA2_FP16 or FA2_BF16 tiles (fp16 / bf16), not FA2_FP32");
+    return FA2_OK;
+}
+// the causal plans have one kernel instance each: an override that asks for another is an error
+int check_causal_plan(bool fwd) {
+    if (const char* n = fa2::causal_override(fwd, !fwd))
+        return fail(FA2_E_INVALID, std::string("launch-plan override ") + n + " cannot be honoured with a causal mask");
+    return FA2_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int fa2_forward_masked(const float* q, const float* k, const float* v, float* o, float* lse, int B, int H, int S,
+                       int D, int precision, int mask, void* stream) {
+    int rc;
+    if ((rc = check_shape(B, H, S, D)) || (rc = check_precision(precision)) || (rc = check_mask(mask, precision)) ||
+        (rc = check_ptrs({q, k, v, o, lse})))
+        return rc;
+    if (mask == FA2_MASK_NONE) return fa2_forward(q, k, v, o, lse, B, H, S, D, precision, stream);
+    if ((rc = check_causal_plan(true))) return rc;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const hipError_t e = precision == FA2_FP16 ? fa2::launch_forward_causal_f16(D, q, k, v, o, lse, B * H, S, st)
+                                               : fa2::launch_forward_causal_bf16(D, q, k, v, o, lse, B * H, S, st);
+    return hip_status(e, "fa2_forward_masked launch");
+}
+
+int fa2_backward_masked(const float* q, const float* k, const float* v, const float* o, const float* dout,
+                        const float* lse, float* delta, float* dq, float* dk, float* dv, int B, int H, int S, int D,
+                        int precision, int mask, void* stream) {
+    int rc;
+    if ((rc = check_shape(B, H, S, D)) || (rc = check_precision(precision)) || (rc = check_mask(mask, precision)) ||
+        (rc = check_ptrs({q, k, v, o, dout, lse, delta, dq, dk, dv})))
+        return rc;
+    if (mask == FA2_MASK_NONE) return fa2_backward(q, k, v, o, dout, lse, delta, dq, dk, dv, B, H, S, D, precision, stream);
+    if ((rc = check_causal_plan(false))) return rc;
+    const int part = fa2::tune_knob("BWD_CAUSAL_PART", 0);
+    if (part < 0 || part > 2) return fail(FA2_E_INVALID, "BWD_CAUSAL_PART must be 0, 1 or 2");
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const hipError_t e =
+        precision == FA2_FP16
+            ? fa2::launch_backward_causal_f16(D, q, k, v, o, dout, lse, delta, dq, dk, dv, B * H, S, st, part)
+            : fa2::launch_backward_causal_bf16(D, q, k, v, o, dout, lse, delta, dq, dk, dv, B * H, S, st, part);
+    return hip_status(e, "fa2_backward_masked launch");
 }
 
 int fa2_backward_dkdv(const float* q, const float* k, const float* v, const float* dout, const float* lse,

@@ -26,6 +26,8 @@ KERNEL_DIR = os.path.join(PKG_ROOT, "kernels")
 FA2_FP16 = 0
 FA2_FP32 = 1
 FA2_BF16 = 2
+FA2_MASK_NONE = 0
+FA2_MASK_CAUSAL = 1
 _PRECISION = {"fp16": FA2_FP16, "fp32": FA2_FP32, "bf16": FA2_BF16,
               FA2_FP16: FA2_FP16, FA2_FP32: FA2_FP32, FA2_BF16: FA2_BF16}
 SUPPORTED_HEAD_DIMS = (32, 64, 128)
@@ -35,12 +37,12 @@ C_SYMBOLS = (
     "fa2_forward", "fa2_delta", "fa2_backward", "fa2_backward_dkdv",
     "fa2_backward_dq", "fa2_backward_dq_delta", "fa2_naive_forward", "fa2_fa1_forward",
     "fa2_forward_host", "fa2_backward_host", "fa2_host_release", "fa2_shard_range", "fa2_tune_set", "fa2_tune_get", "fa2_last_error",
-    "fa2_version", "fa2_build_id", "fa2_device_count",
+    "fa2_version", "fa2_build_id", "fa2_device_count", "fa2_forward_masked", "fa2_backward_masked",
 )
 # launch-plan overrides fa2_tune_set accepts (include/fa2_amd.h)
 KNOBS = ("FWD_HS", "FWD_WAVES", "FWD_KS", "FWD_NKB", "DKDV_WAVES", "DKDV_QS", "DKDV_HS", "DQ_WAVES", "DQ_KS", "DQ_HS",
          "BWD_FUSED", "BWD_FUSED_DELTA", "BWD_FQS", "BWD_FKS", "BWD_FNW", "HOST_SHARDS_ON_DEVICE0", "HOST_CHUNKS",
-         "FWD_SPLIT", "BWD_SPLIT")
+         "FWD_SPLIT", "BWD_SPLIT", "BWD_CAUSAL_PART")
 
 
 class FA2Error(RuntimeError):
@@ -89,6 +91,8 @@ def _load(path):
         "fa2_forward": [P] * 5 + [I] * 5 + [V],
         "fa2_delta": [P] * 3 + [I] * 4 + [V],
         "fa2_backward": [P] * 10 + [I] * 5 + [V],
+        "fa2_forward_masked": [P] * 5 + [I] * 6 + [V],
+        "fa2_backward_masked": [P] * 10 + [I] * 6 + [V],
         "fa2_backward_dkdv": [P] * 8 + [I] * 4 + [V],
         "fa2_backward_dq": [P] * 7 + [I] * 4 + [V],
         "fa2_backward_dq_delta": [P] * 8 + [I] * 4 + [V],
@@ -245,15 +249,20 @@ def _shape(q):
     return B, H, S, D
 
 
-def forward(q, k, v, precision="fp16", out=None, lse=None, stream=None):
-    """O, LSE = FA2 forward.  Replaces the reference's fwd kernel launch."""
+def forward(q, k, v, precision="fp16", out=None, lse=None, stream=None, causal=False):
+    """O, LSE = FA2 forward.  Replaces the reference's fwd kernel launch.
+    ``causal=True``: row i attends keys j <= i (fa2_forward_masked; fp16 / bf16 tiles)."""
     import torch
 
     B, H, S, D = _shape(q)
     out = torch.empty_like(q) if out is None else out
     lse = torch.empty((B, H, S), device=q.device, dtype=torch.float32) if lse is None else lse
     ptrs = _ptrs(((q, "q", 4), (k, "k", 4), (v, "v", 4), (out, "out", 4), (lse, "lse", 3)), B, H, S, D, q.device)
-    _check(lib().fa2_forward(*ptrs, B, H, S, D, _PRECISION[precision], _stream(stream, q.device)))
+    if causal:
+        _check(lib().fa2_forward_masked(*ptrs, B, H, S, D, _PRECISION[precision], FA2_MASK_CAUSAL,
+                                        _stream(stream, q.device)))
+    else:
+        _check(lib().fa2_forward(*ptrs, B, H, S, D, _PRECISION[precision], _stream(stream, q.device)))
     return out, lse
 
 
@@ -267,8 +276,10 @@ def delta(dout, o, out=None, stream=None):
     return out
 
 
-def backward(q, k, v, o, dout, lse, precision="fp16", dq=None, dk=None, dv=None, delta_buf=None, stream=None):
-    """dQ, dK, dV = FA2 backward (Δ computed internally into ``delta_buf``)."""
+def backward(q, k, v, o, dout, lse, precision="fp16", dq=None, dk=None, dv=None, delta_buf=None, stream=None,
+             causal=False):
+    """dQ, dK, dV = FA2 backward (Δ computed internally into ``delta_buf``).
+    ``causal=True``: the backward of the causal forward (fa2_backward_masked)."""
     import torch
 
     B, H, S, D = _shape(q)
@@ -278,7 +289,11 @@ def backward(q, k, v, o, dout, lse, precision="fp16", dq=None, dk=None, dv=None,
     delta_buf = torch.empty((B, H, S), device=q.device, dtype=torch.float32) if delta_buf is None else delta_buf
     ptrs = _ptrs(((q, "q", 4), (k, "k", 4), (v, "v", 4), (o, "o", 4), (dout, "dout", 4), (lse, "lse", 3),
                   (delta_buf, "delta", 3), (dq, "dq", 4), (dk, "dk", 4), (dv, "dv", 4)), B, H, S, D, q.device)
-    _check(lib().fa2_backward(*ptrs, B, H, S, D, _PRECISION[precision], _stream(stream, q.device)))
+    if causal:
+        _check(lib().fa2_backward_masked(*ptrs, B, H, S, D, _PRECISION[precision], FA2_MASK_CAUSAL,
+                                         _stream(stream, q.device)))
+    else:
+        _check(lib().fa2_backward(*ptrs, B, H, S, D, _PRECISION[precision], _stream(stream, q.device)))
     return dq, dk, dv
 
 

@@ -427,10 +427,13 @@ constexpr int kIglpDkdv = 0, kIglpDq = -1;
 // with split queries (S = 512: 16.0 us without), and with unsplit queries (4-8 blocks per
 // CU) strategy 0 is better (B2_H8_S2048 64.4 -> 62.7 us); the dQ role +-1 % either way.
 constexpr int kIglpFused = 2;
-template <int D, int IGLP = -1, typename Mid>
+// CAUSAL: the one step that overlaps the wave's keys; scores of keys after their query
+// (q0s = the step's first query, key = the lane's first key, + 16 nb) are -inf before the
+// exponential, so P and dS are exactly 0 there.
+template <int D, int IGLP = -1, bool CAUSAL = false, typename Mid>
 __device__ __forceinline__ void dkdv_step16(DkdvState16<D>& st, const _Float16* Qs, const _Float16* dOs,
                                             const float* nlse2, const float* ndel, const FragOffsets16<D>& fo,
-                                            int g, Mid&& mid) {
+                                            int g, Mid&& mid, int q0s = 0, int key = 0) {
 #pragma unroll
     for (int qb = 0; qb < 2; ++qb) {
         if (qb == 1) mid();
@@ -457,6 +460,15 @@ __device__ __forceinline__ void dkdv_step16(DkdvState16<D>& st, const _Float16* 
                     da[mb][nb] = mfma16(doa, st.vf[nb][ks], da[mb][nb]);
                 }
             }
+        if (CAUSAL) {
+#pragma unroll
+            for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+                for (int nb = 0; nb < 2; ++nb)
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+                        if (key + 16 * nb > q0s + qb * 32 + 16 * mb + 4 * g + i) sa[mb][nb][i] = -__builtin_inff();
+        }
         f16x8 pf[2], dsf[2];  // [nb], k-slot j <-> query 16 (j >> 2) + 4g + (j & 3)
 #pragma unroll
         for (int nb = 0; nb < 2; ++nb)
@@ -538,7 +550,14 @@ struct DkdvLds {
 // the BH * ceil(S / (KPW * NK)) key blocks.
 // DEL: Δ = rowsum(dO ∘ O) of every staged step computed here from O rows staged
 // beside dO (no Delta input: the fused small-grid launch, whose dQ role writes Δ).
-template <int D, int NW, int KB = 1, bool M16 = false, int QS = 1, bool DEL = false, int IGLP = -1>
+// CAUSAL (16x16x32, QS = 1): queries before the workgroup's first key contribute nothing,
+// so the step loop starts at kblock0 / 64.  A wave (keys key0 .. key0 + 31) skips the
+// steps that end before key0 (it still stages and takes the barrier), masks the one step
+// that overlaps its keys and runs the later ones unmasked: the first 32 NK / 64 steps
+// carry the per-wave choice, the rest run the unchanged loop body.  Every key j < S is
+// attended at least by query j, so every dK / dV row comes out of the normal epilogue.
+template <int D, int NW, int KB = 1, bool M16 = false, int QS = 1, bool DEL = false, int IGLP = -1,
+          bool CAUSAL = false>
 __device__ __forceinline__ void dkdv_body(char* __restrict__ lds, int bid, const float* __restrict__ Q,
                                           const float* __restrict__ K, const float* __restrict__ V,
                                           const float* __restrict__ dO, const float* __restrict__ LSE,
@@ -550,6 +569,7 @@ __device__ __forceinline__ void dkdv_body(char* __restrict__ lds, int bid, const
     constexpr int TILE = L::TILE;
     constexpr int KPW = 32 * KB;  // keys per wave
     static_assert(QS == 1 || (M16 && 2 * QS <= NW), "query split: 16x16x32, 2 QS row waves");
+    static_assert(!CAUSAL || (M16 && QS == 1 && !DEL), "causal: 16x16x32, unsplit queries, Delta given");
     constexpr int NK = L::NK;  // key waves (QS > 1: waves w, w + NK, ... share keys)
     _Float16* smem = reinterpret_cast<_Float16*>(lds);
     float(*rows)[2][QS * QT] = reinterpret_cast<float(*)[2][QS * QT]>(lds + L::ROWS);
@@ -699,12 +719,13 @@ __device__ __forceinline__ void dkdv_body(char* __restrict__ lds, int bid, const
     };
     const int nqt = (S + QT - 1) / QT;  // query tiles
     const int nsteps = (nqt + QS - 1) / QS;
+    const int it0 = CAUSAL ? kblock0 / QT : 0;  // first step (even: kblock0 is a multiple of 32 NK)
     if (stg) {
-        qs.load(0);
-        dos.load(0);
-        if constexpr (DEL) os.load(0);
+        qs.load(it0 * QS * QT);
+        dos.load(it0 * QS * QT);
+        if constexpr (DEL) os.load(it0 * QS * QT);
     }
-    load_rows(0);
+    load_rows(it0 * QS * QT);
     if constexpr (L::OVL) {
         kst.store(smem, kscale, tid);
         vst.store(vblk, 1.f, tid);
@@ -713,7 +734,7 @@ __device__ __forceinline__ void dkdv_body(char* __restrict__ lds, int bid, const
         read_v();
         __syncthreads();
     }
-    store_step(smem, smem + QS * TILE, 0, 0);
+    store_step(smem, smem + QS * TILE, 0, it0);
     __syncthreads();
     // the group's tile within each staged image: folded into the per-lane offsets
     if (QS > 1) fo16.shift(qg * TILE);
@@ -730,7 +751,32 @@ __device__ __forceinline__ void dkdv_body(char* __restrict__ lds, int bid, const
             dkdv_step<D, KB>(st, Qb, dOb, r0, r1, fo, h, mid);
         }
     };
-    for (int it = 0; it < nsteps; it += 2) {
+    int itf = 0;  // first step of the unmasked loop
+    if constexpr (CAUSAL) {
+        static_assert(!CAUSAL || (32 * NK) % (2 * QT) == 0, "causal: an even number of 64-query steps per key block");
+        const int itd = __builtin_amdgcn_readfirstlane(key0 / QT);  // the step that overlaps this wave's keys
+        const int klane = key0 + (lane & 15);
+        auto stepc = [&](int b, int it) __attribute__((always_inline)) {  // b: the step's buffer pair
+            const bool more = it + 1 < nsteps;
+            auto mid = [&] { if (more) load_next(it + 1); };
+            const _Float16* Qb = smem + 2 * b * TILE;
+            // The next step's loads go out before the branch, not inside both of its sides
+            // (joined there, the staging registers' copies spilled ~280 VGPRs at D = 64).  One
+            // masked body serves the step on the wave's keys and the later ones of these few
+            // steps, where the compare never hits.
+            mid();
+            if (it >= itd)
+                dkdv_step16<D, IGLP, true>(st16, Qb, Qb + TILE, rows[b][0], rows[b][1], fo16, g16, [] {}, it * QT, klane);
+            if (more) store_step(smem + 2 * (1 - b) * TILE, smem + (2 * (1 - b) + 1) * TILE, 1 - b, it + 1);
+            __syncthreads();
+        };
+        itf = it0 + 32 * NK / QT < nsteps ? it0 + 32 * NK / QT : nsteps;
+        for (int it = it0; it < itf; it += 2) {
+            stepc(0, it);
+            if (it + 1 < itf) stepc(1, it + 1);
+        }
+    }
+    for (int it = itf; it < nsteps; it += 2) {
         {
             const bool more = it + 1 < nsteps;
             run_step(smem, smem + QS * TILE, rows[0][0], rows[0][1], it, [&] { if (more) load_next(it + 1); });
@@ -792,15 +838,39 @@ __device__ __forceinline__ void dkdv_body(char* __restrict__ lds, int bid, const
     }
 }
 
-template <int D, int NW, int KB = 1, bool M16 = false, int QS = 1>
+// The causal kernels' blocks of one workgroup: `body(bid)` for block bid of the BH * nb
+// blocks.  pair = 1: the workgroup takes two blocks of its head, p and nb - 1 - p (one when
+// they coincide) -- a long and a short one, so every workgroup of a head runs the same number
+// of tiles (grid BH * ceil(nb / 2)); pair = 0: one block per workgroup (grid BH * nb).
+template <typename Body>
+__device__ __forceinline__ void causal_blocks(int nb, int pair, Body&& body) {
+    const int wg = xcd_remap(blockIdx.x, gridDim.x);
+    const int per = pair ? (nb + 1) / 2 : nb;  // workgroups per head
+    const int bh = wg / per, p = wg - bh * per;
+    for (int pass = 0; pass <= pair; ++pass) {
+        const int b = pass ? nb - 1 - p : p;
+        if (pass && b == p) break;
+        body(bh * nb + b);
+        __syncthreads();  // the next block restages the LDS buffers
+    }
+}
+
+template <int D, int NW, int KB = 1, bool M16 = false, int QS = 1, bool CAUSAL = false>
 __global__ void __launch_bounds__(64 * NW)
 fa2_bwd_dkdv_f16_kernel(const float* __restrict__ Q, const float* __restrict__ K, const float* __restrict__ V,
                         const float* __restrict__ dO, const float* __restrict__ LSE,
-                        const float* __restrict__ Delta, float* __restrict__ dK, float* __restrict__ dV, int S) {
+                        const float* __restrict__ Delta, float* __restrict__ dK, float* __restrict__ dV, int S,
+                        int pair) {
     __shared__ __attribute__((aligned(16))) char lds[DkdvLds<D, NW, KB, QS>::BYTES];
     // the unsplit instances (full grids: C3, C5, long S) under an LLVM scheduling strategy
-    dkdv_body<D, NW, KB, M16, QS, false, QS == 1 && D == 64 ? kIglpDkdv : -1>(lds, xcd_remap(blockIdx.x, gridDim.x),
-                                                                                 Q, K, V, dO, LSE, Delta, dK, dV, S);
+    constexpr int IGLP = QS == 1 && D == 64 ? kIglpDkdv : -1;
+    if constexpr (CAUSAL)
+        causal_blocks((S + 32 * KB * NW - 1) / (32 * KB * NW), pair, [&](int bid) {
+            dkdv_body<D, NW, KB, M16, QS, false, IGLP, true>(lds, bid, Q, K, V, dO, LSE, Delta, dK, dV, S);
+        });
+    else
+        dkdv_body<D, NW, KB, M16, QS, false, IGLP>(lds, xcd_remap(blockIdx.x, gridDim.x), Q, K, V, dO, LSE, Delta, dK,
+                                                  dV, S);
 }
 
 // ---------------------------------------------------------------------------
@@ -851,6 +921,11 @@ __device__ __forceinline__ void dq_tile(DqState<D>& st, const _Float16* Ks, cons
 //     B = Q / dO fragments in VGPRs; accumulators start at the lane's -lse2 / -delta.
 //   dQ^T (m = d, n = query, k = key): B = dS^T packed k-slot j <-> key
 //     16 (j >> 2) + 4g + (j & 3) of each 32-key half; A = K^T by transposed reads.
+template <bool T>
+struct CausalTag {
+    static constexpr bool value = T;
+};
+
 template <int D>
 struct DqState16 {
     f16x8 qf[2][D / 32], df[2][D / 32];  // [nb][ks]: Q (scaled) / dO[query 16 nb + (l&15)][d 32 ks + 8g ..]
@@ -858,9 +933,11 @@ struct DqState16 {
     f32x4 nlse2[2], ndel[2];             // [nb]: splats of the lane's -lse2 / -delta
 };
 
-template <int D, bool MASK, int NKB, int IGLP = -1, typename Mid>
+// CAUSAL (MASK tiles only): keys after their query (the lane's first row `qrow`, + 16 nb)
+// are masked too -- the wave's diagonal tile.
+template <int D, bool MASK, int NKB, int IGLP = -1, bool CAUSAL = false, typename Mid>
 __device__ __forceinline__ void dq_tile16(DqState16<D>& st, const _Float16* Ks, const _Float16* Vs,
-                                          const FragOffsets16<D>& fo, int k0, int S, int g, Mid&& mid) {
+                                          const FragOffsets16<D>& fo, int k0, int S, int g, Mid&& mid, int qrow = 0) {
     f16x8 dsf[NKB][2];  // [32-key half kb][nb]
 #pragma unroll
     for (int kb = 0; kb < NKB; ++kb) {
@@ -885,14 +962,16 @@ __device__ __forceinline__ void dq_tile16(DqState16<D>& st, const _Float16* Ks, 
                     da[mbl][nb] = mfma16(va, st.df[nb][ks], da[mbl][nb]);
                 }
             }
-        if (MASK) {  // ragged last tile only
+        if (MASK) {  // ragged last tile (and the causal diagonal tile) only
 #pragma unroll
             for (int mbl = 0; mbl < 2; ++mbl)
 #pragma unroll
                 for (int nb = 0; nb < 2; ++nb)
 #pragma unroll
-                    for (int i = 0; i < 4; ++i)
-                        if (k0 + 32 * kb + 16 * mbl + 4 * g + i >= S) sa[mbl][nb][i] = -__builtin_inff();
+                    for (int i = 0; i < 4; ++i) {
+                        const int key = k0 + 32 * kb + 16 * mbl + 4 * g + i;
+                        if (key >= S || (CAUSAL && key > qrow + 16 * nb)) sa[mbl][nb][i] = -__builtin_inff();
+                    }
         }
         if (NKB == 1) mid();  // 32-key tiles: after the tile's S / dP MFMAs
 #pragma unroll
@@ -940,7 +1019,13 @@ struct DqLds {
 
 // One workgroup of the dQ kernel; `bid` is its (XCD-remapped) block number over the
 // BH * ceil(S / (32 * NQ)) query blocks.
-template <int D, int NW, bool DELTA = false, int NKB = 2, bool M16 = false, int KS = 1, int IGLP = -1>
+// CAUSAL (16x16x32, KS = 1, 64-key tiles): as in the forward -- the workgroup stages only
+// the tiles up to the one that holds its last row; a wave runs the tiles before its
+// diagonal tile unmasked, masks the diagonal tile per element and skips the later ones
+// (staging and taking the barrier).  The steps before the workgroup's first row are full
+// for every wave and keep the loop body without the per-wave choice.
+template <int D, int NW, bool DELTA = false, int NKB = 2, bool M16 = false, int KS = 1, int IGLP = -1,
+          bool CAUSAL = false>
 __device__ __forceinline__ void dq_body(char* __restrict__ lds, int bid, const float* __restrict__ Q,
                                         const float* __restrict__ K, const float* __restrict__ V,
                                         const float* __restrict__ dO, const float* __restrict__ LSE,
@@ -952,6 +1037,7 @@ __device__ __forceinline__ void dq_body(char* __restrict__ lds, int bid, const f
     constexpr int NT = 64 * NW;
     constexpr int TILE = L::TILE;
     static_assert(KS == 1 || (M16 && NW % KS == 0), "key split: 16x16x32");
+    static_assert(!CAUSAL || (M16 && KS == 1 && NKB == 2), "causal: 16x16x32, unsplit keys, 64-key tiles");
     constexpr int NQ = L::NQ;  // query waves (KS > 1: waves w, w + NQ, ... share rows)
     _Float16* smem = reinterpret_cast<_Float16*>(lds);
     float(*ostage)[32][36] = reinterpret_cast<float(*)[32][36]>(lds + L::OSTAGE);  // per-wave dQ stage
@@ -1087,6 +1173,52 @@ __device__ __forceinline__ void dq_body(char* __restrict__ lds, int bid, const f
     // the group's tile within each staged image: folded into the per-lane offsets
     if (KS > 1) fo16.shift(kg * TILE);
 
+    if constexpr (CAUSAL) {
+        const int bend = (qb + 1) * 32 * NQ < S ? (qb + 1) * 32 * NQ : S;  // the workgroup's rows end here
+        const int nst = (bend + KT - 1) / KT;                              // ... inside tile nst - 1
+        const int jd = __builtin_amdgcn_readfirstlane((qb * 32 * NQ + (tid >> 6) * 32) / KT);  // diagonal tile
+        const int qlane = qb * 32 * NQ + wave * 32 + i16;
+        // b: the step's buffer pair; TAIL: one of the last steps (full, diagonal or skipped per wave)
+        auto stepc = [&](auto ct, int b, int j) __attribute__((always_inline)) {
+            constexpr bool TAIL = decltype(ct)::value;
+            const bool more = j + 1 < nst;
+            // issued on the last step too (FA2_DKDV_SW's note), there past S: zeros, no traffic
+            const int nrow = more ? (j + 1) * KT : ntiles * KT;
+            auto mid = [&] {
+                ks.load(nrow);
+                vs.load(nrow);
+            };
+            const _Float16* Kc = smem + 2 * b * TILE;
+            if constexpr (TAIL) {
+                // the loads before the branch, not inside each of its sides (no joins of the
+                // staging registers)
+                mid();
+                if (j > jd) {
+                } else if (j == jd || j == last_ragged) {
+                    dq_tile16<D, true, NKB, IGLP, true>(st16, Kc, Kc + TILE, fo16, j * KT, S, g16, [] {}, qlane);
+                } else {
+                    dq_tile16<D, false, NKB, IGLP>(st16, Kc, Kc + TILE, fo16, j * KT, S, g16, [] {});
+                }
+            } else {
+                dq_tile16<D, false, NKB, IGLP>(st16, Kc, Kc + TILE, fo16, j * KT, S, g16, mid);
+            }
+            if (more) {
+                ks.store(smem + 2 * (1 - b) * TILE, 1.f, tid);
+                vs.store(smem + (2 * (1 - b) + 1) * TILE, 1.f, tid);
+            }
+            __syncthreads();
+        };
+        static_assert(!CAUSAL || (32 * NQ) % (2 * KT) == 0, "causal: an even number of tiles per query block");
+        const int jf = qb * (32 * NQ / KT);  // tiles that end at or before the first row (even, < nst)
+        for (int j = 0; j < jf; j += 2) {
+            stepc(CausalTag<false>{}, 0, j);
+            stepc(CausalTag<false>{}, 1, j + 1);
+        }
+        for (int j = jf; j < nst; j += 2) {
+            stepc(CausalTag<true>{}, 0, j);
+            if (j + 1 < nst) stepc(CausalTag<true>{}, 1, j + 1);
+        }
+    } else
     for (int j = 0; j < nsteps; j += 2) {
         {
             const bool more = j + 1 < nsteps;
@@ -1447,14 +1579,20 @@ fa2_bwd_split_reduce_kernel(const float* __restrict__ part, int P, long n, float
 }
 #endif  // CUPY_INLINE_COMPILE
 
-template <int D, int NW, bool DELTA = false, int NKB = 2, bool M16 = false, int KS = 1>
+template <int D, int NW, bool DELTA = false, int NKB = 2, bool M16 = false, int KS = 1, bool CAUSAL = false>
 __global__ void __launch_bounds__(64 * NW)
 fa2_bwd_dq_f16_kernel(const float* __restrict__ Q, const float* __restrict__ K, const float* __restrict__ V,
                       const float* __restrict__ dO, const float* __restrict__ LSE, float* __restrict__ Delta,
-                      float* __restrict__ dQ, int S, const float* __restrict__ O) {
+                      float* __restrict__ dQ, int S, const float* __restrict__ O, int pair) {
     __shared__ __attribute__((aligned(16))) char lds[DqLds<D, NW, DELTA, NKB, KS>::BYTES];
-    dq_body<D, NW, DELTA, NKB, M16, KS, KS == 1 && D == 64 ? kIglpDq : -1>(
-        lds, xcd_remap(blockIdx.x, gridDim.x), Q, K, V, dO, LSE, Delta, dQ, S, O);
+    constexpr int IGLP = KS == 1 && D == 64 ? kIglpDq : -1;
+    if constexpr (CAUSAL)
+        causal_blocks((S + 32 * NW - 1) / (32 * NW), pair, [&](int bid) {
+            dq_body<D, NW, DELTA, NKB, M16, KS, IGLP, true>(lds, bid, Q, K, V, dO, LSE, Delta, dQ, S, O);
+        });
+    else
+        dq_body<D, NW, DELTA, NKB, M16, KS, IGLP>(lds, xcd_remap(blockIdx.x, gridDim.x), Q, K, V, dO, LSE, Delta, dQ, S,
+                                                  O);
 }
 
 // dK/dV and dQ in ONE launch (small grids).  Workgroups [0, ndk) take the dK/dV role
@@ -1712,7 +1850,7 @@ hipError_t dkdv_launch(const float* q, const float* k, const float* v, const flo
     const long grid = (long)bh * ((S + 32 * (NW / QS) - 1) / (32 * (NW / QS)));
     if (grid <= 0 || grid > 0x7fffffffL) return hipErrorInvalidValue;
     hipLaunchKernelGGL((fa2f16b::fa2_bwd_dkdv_f16_kernel<D, NW, 1, M16, QS>), dim3((unsigned)grid), dim3(64 * NW), 0,
-                       stream, q, k, v, dout, lse, delta, dk, dv, S);
+                       stream, q, k, v, dout, lse, delta, dk, dv, S, 0);
     return hipGetLastError();
 }
 // Geometry: 8 waves x 32 keys for D <= 64 (2 waves/SIMD in 256 VGPRs); D = 128 4 x 32
@@ -1778,10 +1916,10 @@ hipError_t dq_launch(const float* q, const float* k, const float* v, const float
     if (grid <= 0 || grid > 0x7fffffffL) return hipErrorInvalidValue;
     if (o)
         hipLaunchKernelGGL((fa2f16b::fa2_bwd_dq_f16_kernel<D, NW, true, NKB, M16, KS>), dim3((unsigned)grid),
-                           dim3(64 * NW), 0, stream, q, k, v, dout, lse, delta, dq, S, o);
+                           dim3(64 * NW), 0, stream, q, k, v, dout, lse, delta, dq, S, o, 0);
     else
         hipLaunchKernelGGL((fa2f16b::fa2_bwd_dq_f16_kernel<D, NW, false, NKB, M16, KS>), dim3((unsigned)grid),
-                           dim3(64 * NW), 0, stream, q, k, v, dout, lse, delta, dq, S, o);
+                           dim3(64 * NW), 0, stream, q, k, v, dout, lse, delta, dq, S, o, 0);
     return hipGetLastError();
 }
 template <int D>
@@ -2024,6 +2162,42 @@ static hipError_t bwd_split_plan(int D, const float* q, const float* k, const fl
 // which reads it; -1 (default) = 1 on grids of fewer than 8 blocks of 32 rows per
 // CU.  Measured (fwd + bwd step, B2_H8_D64, r01): S = 512 31.1 -> 27.0 us, 1024
 // 50.1 -> 48.2, 2048 108.7 -> 106.0; S = 4096 282 -> 286 and C3 +-0 (so unfused).
+namespace {
+// Causal backward: dQ with Δ fused (16x16x32, 64-key tiles, unsplit), then dK/dV
+// (16x16x32, unsplit queries); 8 waves at D <= 64, 4 at D = 128, on every grid size.
+template <int D>
+hipError_t causal_backward(const float* q, const float* k, const float* v, const float* o, const float* dout,
+                           const float* lse, float* delta, float* dq, float* dk, float* dv, int bh, int S,
+                           hipStream_t stream, int part) {
+    constexpr int NW = D <= 64 ? 8 : 4;
+    const int nb = (S + 32 * NW - 1) / (32 * NW);  // query blocks (dQ) and key blocks (dK/dV) per head
+    // balanced pairs of blocks per workgroup where their grid still covers every CU
+    const int pair = causal_pairs(bh, nb);
+    const long grid = (long)bh * (pair ? (nb + 1) / 2 : nb);
+    if (grid <= 0 || grid > 0x7fffffffL) return hipErrorInvalidValue;
+    if (part != 2)
+        hipLaunchKernelGGL((fa2f16b::fa2_bwd_dq_f16_kernel<D, NW, true, 2, true, 1, true>), dim3((unsigned)grid),
+                           dim3(64 * NW), 0, stream, q, k, v, dout, lse, delta, dq, S, o, pair);
+    if (part != 1)
+        hipLaunchKernelGGL((fa2f16b::fa2_bwd_dkdv_f16_kernel<D, NW, 1, true, 1, true>), dim3((unsigned)grid),
+                           dim3(64 * NW), 0, stream, q, k, v, dout, lse, delta, dk, dv, S, pair);
+    return hipGetLastError();
+}
+}  // namespace
+
+hipError_t FA2_TILE_LAUNCH(launch_backward_causal)(int D, const float* q, const float* k, const float* v,
+                                                   const float* o, const float* dout, const float* lse, float* delta,
+                                                   float* dq, float* dk, float* dv, int bh, int S, hipStream_t stream,
+                                                   int part) {
+    if (bh <= 0 || S <= 0 || part < 0 || part > 2 || causal_override(false, true)) return hipErrorInvalidValue;
+    switch (D) {
+        case 32: return causal_backward<32>(q, k, v, o, dout, lse, delta, dq, dk, dv, bh, S, stream, part);
+        case 64: return causal_backward<64>(q, k, v, o, dout, lse, delta, dq, dk, dv, bh, S, stream, part);
+        case 128: return causal_backward<128>(q, k, v, o, dout, lse, delta, dq, dk, dv, bh, S, stream, part);
+        default: return hipErrorInvalidValue;
+    }
+}
+
 hipError_t FA2_TILE_LAUNCH(launch_backward)(int D, const float* q, const float* k, const float* v, const float* o,
                                const float* dout, const float* lse, float* delta, float* dq, float* dk, float* dv,
                                int bh, int S, hipStream_t stream) {

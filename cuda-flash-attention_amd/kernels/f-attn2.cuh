@@ -120,6 +120,30 @@ hipError_t launch_bwd_dq_delta_bf16(int D, const float* q, const float* k, const
                                     const float* dout, const float* lse, float* delta, float* dq, int bh, int S,
                                     hipStream_t stream);
 
+// Causal (lower-triangular) mask, fp16 / bf16 tiles: query row i attends keys j <= i.
+// One compiler-scheduled geometry per head dim on every grid size; the backward runs dQ
+// (Δ fused, written to `delta`) and then dK/dV.  No scratch.  `part` (tools): 0 = both
+// kernels, 1 = dQ + Δ only, 2 = dK/dV only (Δ read from `delta`).
+hipError_t launch_forward_causal_f16(int D, const float* q, const float* k, const float* v, float* o, float* lse,
+                                     int bh, int S, hipStream_t stream);
+hipError_t launch_forward_causal_bf16(int D, const float* q, const float* k, const float* v, float* o, float* lse,
+                                      int bh, int S, hipStream_t stream);
+hipError_t launch_backward_causal_f16(int D, const float* q, const float* k, const float* v, const float* o,
+                                      const float* dout, const float* lse, float* delta, float* dq, float* dk,
+                                      float* dv, int bh, int S, hipStream_t stream, int part);
+hipError_t launch_backward_causal_bf16(int D, const float* q, const float* k, const float* v, const float* o,
+                                       const float* dout, const float* lse, float* delta, float* dq, float* dk,
+                                       float* dv, int bh, int S, hipStream_t stream, int part);
+// The launch-plan override set now that the causal forward (fwd) / backward (bwd) plan
+// cannot honour, or nullptr: the causal plans have one instance each, so any override
+// that picks another kernel, geometry or split is an error, never silently dropped.
+const char* causal_override(bool fwd, bool bwd);
+// Causal launches: 1 when a workgroup takes a balanced pair of its head's `nb` blocks (p and
+// nb - 1 - p; every workgroup then runs the same number of tiles), 0 for one block per
+// workgroup -- where the grid of pairs would no longer cover every CU.
+int cu_count();
+inline int causal_pairs(int bh, int nb) { return nb > 1 && (long)bh * ((nb + 1) / 2) >= cu_count() ? 1 : 0; }
+
 inline bool supported_head_dim(int D) { return D == 32 || D == 64 || D == 128; }
 
 // Launch-plan override `name` as set by fa2_tune_set (include/fa2_amd.h), else `dflt`

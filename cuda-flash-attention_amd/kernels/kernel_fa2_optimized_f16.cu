@@ -353,17 +353,22 @@ __device__ __forceinline__ void fwd_exp(const f32x16 (&sacc)[NKB], float sh, f16
 // O^T += V^T P^T with the packed scores as the B operand (each V^T fragment feeds MQ
 // MFMAs).  first: the wave's first tile (m := its row max).  One slow-path decision
 // for all groups keeps the tile a single basic block on the common path.
-template <int D, int MQ, bool MASK, int NKB = 2, bool SEED = true>
+// CAUSAL (MASK tiles only): keys after the lane's query row `qrow` are masked too -- the
+// wave's diagonal tile (MQ == 1: one query per lane).
+template <int D, int MQ, bool MASK, int NKB = 2, bool SEED = true, bool CAUSAL = false>
 __device__ __forceinline__ void fwd_softmax_pv(FwdState<D> (&st)[MQ], f32x16 (&sacc)[MQ][NKB], const _Float16* Vs,
-                                               const FragOffsets<D>& fo, int k0, int S, int h, bool first) {
-    if (MASK) {  // ragged last tile only
+                                               const FragOffsets<D>& fo, int k0, int S, int h, bool first,
+                                               int qrow = 0) {
+    if (MASK) {  // ragged last tile (and the causal diagonal tile) only
 #pragma unroll
         for (int g = 0; g < MQ; ++g)
 #pragma unroll
             for (int kb = 0; kb < NKB; ++kb)
 #pragma unroll
-                for (int i = 0; i < 16; ++i)
-                    if (k0 + kb * 32 + (i & 3) + 8 * (i >> 2) + 4 * h >= S) sacc[g][kb][i] = -__builtin_inff();
+                for (int i = 0; i < 16; ++i) {
+                    const int key = k0 + kb * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
+                    if (key >= S || (CAUSAL && key > qrow)) sacc[g][kb][i] = -__builtin_inff();
+                }
     }
     f16x8 pf[MQ][NKB][2];
     float ls[MQ][4];
@@ -425,17 +430,19 @@ __device__ __forceinline__ void fwd_softmax_pv(FwdState<D> (&st)[MQ], f32x16 (&s
 // m, the tile sums and O^T += V^T P^T, with no rescale branch (no register joins in the
 // tile loop).  Returns whether a half-row sum left [0, 2^13] (or went inf / NaN) in any
 // lane; the caller then redoes the whole query block with the rescaling loop.
-template <int D, int MQ, bool MASK, int NKB = 2, bool SEED = true>
+template <int D, int MQ, bool MASK, int NKB = 2, bool SEED = true, bool CAUSAL = false>
 __device__ __forceinline__ bool fwd_softmax_pv_fast(FwdState<D> (&st)[MQ], f32x16 (&sacc)[MQ][NKB], const _Float16* Vs,
-                                                    const FragOffsets<D>& fo, int k0, int S, int h) {
+                                                    const FragOffsets<D>& fo, int k0, int S, int h, int qrow = 0) {
     if (MASK) {
 #pragma unroll
         for (int g = 0; g < MQ; ++g)
 #pragma unroll
             for (int kb = 0; kb < NKB; ++kb)
 #pragma unroll
-                for (int i = 0; i < 16; ++i)
-                    if (k0 + kb * 32 + (i & 3) + 8 * (i >> 2) + 4 * h >= S) sacc[g][kb][i] = -__builtin_inff();
+                for (int i = 0; i < 16; ++i) {
+                    const int key = k0 + kb * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
+                    if (key >= S || (CAUSAL && key > qrow)) sacc[g][kb][i] = -__builtin_inff();
+                }
     }
     f16x8 pf[MQ][NKB][2];
     float ls[MQ][4];
@@ -531,10 +538,23 @@ __device__ __forceinline__ void fwd_store(const FwdState<D>& st, float* O, float
 // each step stages KS tiles.  The groups' (m, l, O) meet in LDS after the loop
 // (O = Σ_g 2^(m_g - m) O_g, l likewise) and group 0 stores.  That puts NW waves on
 // NQ · 32 query rows, so a grid of few query blocks still covers every SIMD twice.
-template <int D, int NW, int NKB = 2, int KS = 1>
-__global__ void __launch_bounds__(64 * NW)
-fa2_fwd_f16_kernel(const float* __restrict__ Q, const float* __restrict__ K, const float* __restrict__ V,
-                   float* __restrict__ O, float* __restrict__ LSE, int S) {
+//
+// CAUSAL (KS = 1, 64-key tiles): query row i attends keys j <= i.  The workgroup's rows
+// end at `bend`, so it stages only the ceil(bend / 64) tiles up to the one holding its
+// last row.  Rows and tiles are aligned: a wave's 32 rows lie inside ONE tile, its
+// diagonal tile jd.  Tiles before jd are full (the unmasked body), jd is masked per
+// element (key > query, or key >= S, gets -inf before the exponential), tiles after jd are
+// skipped (the wave still stages and takes the barrier).  The steps before the workgroup's
+// first row are full for every wave and run the branch-free loop; only the last
+// 32 NW / 64 steps carry the per-wave choice.  Tile 0 holds key 0 <= every row, so m (its
+// row max) is finite, and every live tile starts at or before the wave's first row, so no
+// live tile has a fully masked row.
+//
+// One query block (head bh, block qb) of the workgroup; the kernel below picks them.
+template <int D, int NW, int NKB, int KS, bool CAUSAL>
+__device__ __forceinline__ void fwd_f16_block(const float* __restrict__ Q, const float* __restrict__ K,
+                                              const float* __restrict__ V, float* __restrict__ O,
+                                              float* __restrict__ LSE, int S, int bh, int qb) {
     constexpr int MQ = 1;            // query groups per wave (2 measured -30 % at D = 32/64: r01)
     constexpr bool SEED = NKB == 2;  // -m seed for 64-key tiles; 32-key tiles subtract m
     constexpr int KT = 32 * NKB;  // keys per tile
@@ -542,6 +562,7 @@ fa2_fwd_f16_kernel(const float* __restrict__ Q, const float* __restrict__ K, con
     constexpr int TILE = KT * D;
     constexpr int QW = 32 * MQ;  // query rows per wave
     static_assert(NW % KS == 0, "key split");
+    static_assert(!CAUSAL || (KS == 1 && NKB == 2), "causal: unsplit keys, 64-key tiles");
     constexpr int NQ = NW / KS;  // query waves (KS > 1: waves w, w + NQ, ... share rows)
     // key-split merge records: per wave of groups 1..KS-1, O (D/2 floats per lane), m, l
     constexpr int MREC = (D / 2 + 2) * 64;
@@ -558,9 +579,6 @@ fa2_fwd_f16_kernel(const float* __restrict__ Q, const float* __restrict__ K, con
     const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, h = lane >> 5;
     const int wave = KS > 1 ? (tid >> 6) % NQ : tid >> 6;  // query slot of the wave
     const int kg = KS > 1 ? __builtin_amdgcn_readfirstlane((tid >> 6) / NQ) : 0;  // key group
-    const int nqb = (S + QW * NQ - 1) / (QW * NQ);
-    const int bid = xcd_remap(blockIdx.x, gridDim.x);
-    const int bh = bid / nqb, qb = bid - bh * nqb;
     const long base = (long)bh * S * D;
     const int q0 = qb * QW * NQ + wave * QW + r;
 
@@ -573,7 +591,11 @@ fa2_fwd_f16_kernel(const float* __restrict__ Q, const float* __restrict__ K, con
     vs.init(V + base, S, tid);
     const int ntiles = (S + KT - 1) / KT;
     const int last_ragged = (S % KT) ? ntiles - 1 : -1;  // the one tile that needs key masking
-    const int nsteps = (ntiles + KS - 1) / KS;
+    // CAUSAL: the tiles up to the one that holds the workgroup's last row (bend <= S)
+    const int bend = (qb + 1) * QW * NQ < S ? (qb + 1) * QW * NQ : S;
+    const int nsteps = CAUSAL ? (bend + KT - 1) / KT : (ntiles + KS - 1) / KS;
+    // CAUSAL: this wave's diagonal tile (wave-uniform)
+    const int jd = CAUSAL ? __builtin_amdgcn_readfirstlane((qb * QW * NQ + (tid >> 6) * QW) / KT) : 0;
     // Q block (32*NQ rows, one contiguous HBM range) loaded row-coalesced, converted
     // and scaled into LDS, then read back as this wave's B fragments: 1 KB per load
     // instruction instead of 32 rows x 32 B per-lane pieces.  OVL (key split: small
@@ -618,7 +640,8 @@ fa2_fwd_f16_kernel(const float* __restrict__ Q, const float* __restrict__ K, con
     auto step = [&](const _Float16* Kc, const _Float16* Vc, _Float16* Kn, _Float16* Vn, int j, bool more,
                     bool redo = true) __attribute__((always_inline)) {
         const int jj = j * KS + kg;                          // this wave's tile
-        const bool live = (KS == 1 || jj < ntiles) && redo;  // wave-uniform (KS > 1: ragged tail)
+        // wave-uniform (KS > 1: ragged tail; CAUSAL: tiles after the diagonal are skipped)
+        const bool live = (KS == 1 || jj < ntiles) && redo && (!CAUSAL || jj <= jd);
         f32x16 sacc[MQ][NKB];
         if (live) fwd_qk<D, MQ, NKB, SEED>(sacc, st, Kc, fo);
         if (more) {
@@ -626,7 +649,8 @@ fa2_fwd_f16_kernel(const float* __restrict__ Q, const float* __restrict__ K, con
             vs.load((j + 1) * KS * KT);
         }
         if (live) {
-            if (jj == last_ragged) fwd_softmax_pv<D, MQ, true, NKB, SEED>(st, sacc, Vc, fo, jj * KT, S, h, j == 0);
+            if (jj == last_ragged || (CAUSAL && jj == jd))
+                fwd_softmax_pv<D, MQ, true, NKB, SEED, CAUSAL>(st, sacc, Vc, fo, jj * KT, S, h, j == 0, q0);
             else fwd_softmax_pv<D, MQ, false, NKB, SEED>(st, sacc, Vc, fo, jj * KT, S, h, j == 0);
         }
         if (more) {
@@ -683,26 +707,74 @@ fa2_fwd_f16_kernel(const float* __restrict__ Q, const float* __restrict__ K, con
             return b;
         };
         step(smem, smem + KS * TILE, smem + 2 * KS * TILE, smem + 3 * KS * TILE, 0, 1 < nsteps);
-        // D <= 64: the ragged last tile's step (always the last one) runs after the loop
-        // (r03 A/B: B2_H8 fwd S = 512 -7 %, S = 1024 -5 %, C3 -1.2 %); D = 128 keeps it
-        // in the loop (peeled, its 32-key-tile loop ran 5.8 % slower at C4)
-        constexpr bool PEEL = D <= 64;
-        using LoopTag = MaskTag<PEEL ? 0 : 1>;
-        // (KS > 1: also a last step where some key group has no tile)
-        const int jend = PEEL && (last_ragged >= 0 || ntiles % KS != 0) && nsteps > 1 ? nsteps - 1 : nsteps;
         bool bad = false;
-        for (int j = 1; j < jend; j += 2) {
-            bad = stepf(LoopTag{}, smem + 2 * KS * TILE, smem + 3 * KS * TILE, smem, smem + KS * TILE, j,
-                        j + 1 < nsteps) ||
-                  bad;
-            if (j + 1 < jend)
-                bad = stepf(LoopTag{}, smem, smem + KS * TILE, smem + 2 * KS * TILE, smem + 3 * KS * TILE, j + 1,
-                            j + 2 < nsteps) ||
+        if constexpr (CAUSAL) {
+            // ct: MaskTag<0>: a step before the workgroup's first row (full for every wave);
+            // MaskTag<1>: one of the last steps, full, diagonal or skipped per wave
+            auto stepc = [&](auto ct, const _Float16* Kc, const _Float16* Vc, _Float16* Kn, _Float16* Vn, int j,
+                             bool more) __attribute__((always_inline)) {
+                constexpr bool TAIL = decltype(ct)::value != 0;
+                const bool live = !TAIL || j <= jd;  // wave-uniform
+                f32x16 sacc[MQ][NKB];
+                if (live) fwd_qk<D, MQ, NKB, SEED>(sacc, st, Kc, fo);
+                if (more) {
+                    ks.load((j + 1) * KT);
+                    vs.load((j + 1) * KT);
+                }
+                bool b = false;
+                if constexpr (TAIL) {
+                    if (live)
+                        b = j == jd || j == last_ragged
+                                ? fwd_softmax_pv_fast<D, MQ, true, NKB, SEED, true>(st, sacc, Vc, fo, j * KT, S, h, q0)
+                                : fwd_softmax_pv_fast<D, MQ, false, NKB, SEED>(st, sacc, Vc, fo, j * KT, S, h);
+                } else {
+                    b = fwd_softmax_pv_fast<D, MQ, false, NKB, SEED>(st, sacc, Vc, fo, j * KT, S, h);
+                }
+                if (more) {
+                    ks.store(Kn, 1.f, tid);
+                    vs.store(Vn, 1.f, tid);
+                }
+                __syncthreads();
+                return b;
+            };
+            _Float16 *const A = smem, *const B = smem + 2 * TILE;  // the two K buffers (V: + TILE)
+            // the tiles that end at or before the workgroup's first row (an even count, below
+            // nsteps: that row's own tile follows): the loop ends on an odd step
+            const int jf = qb * (QW * NQ / KT);
+            for (int j = 1; j < jf; j += 2) {
+                bad = stepc(MaskTag<0>{}, B, B + TILE, A, A + TILE, j, true) || bad;
+                if (j + 1 < jf) bad = stepc(MaskTag<0>{}, A, A + TILE, B, B + TILE, j + 1, true) || bad;
+            }
+            int j = jf > 1 ? jf : 1;
+            if (j & 1) {  // jf = 0: step 1 out of the second pair
+                if (j < nsteps) bad = stepc(MaskTag<1>{}, B, B + TILE, A, A + TILE, j, j + 1 < nsteps) || bad;
+                ++j;
+            }
+            for (; j < nsteps; j += 2) {
+                bad = stepc(MaskTag<1>{}, A, A + TILE, B, B + TILE, j, j + 1 < nsteps) || bad;
+                if (j + 1 < nsteps) bad = stepc(MaskTag<1>{}, B, B + TILE, A, A + TILE, j + 1, j + 2 < nsteps) || bad;
+            }
+        } else {
+            // D <= 64: the ragged last tile's step (always the last one) runs after the loop
+            // (r03 A/B: B2_H8 fwd S = 512 -7 %, S = 1024 -5 %, C3 -1.2 %); D = 128 keeps it
+            // in the loop (peeled, its 32-key-tile loop ran 5.8 % slower at C4)
+            constexpr bool PEEL = D <= 64;
+            using LoopTag = MaskTag<PEEL ? 0 : 1>;
+            // (KS > 1: also a last step where some key group has no tile)
+            const int jend = PEEL && (last_ragged >= 0 || ntiles % KS != 0) && nsteps > 1 ? nsteps - 1 : nsteps;
+            for (int j = 1; j < jend; j += 2) {
+                bad = stepf(LoopTag{}, smem + 2 * KS * TILE, smem + 3 * KS * TILE, smem, smem + KS * TILE, j,
+                            j + 1 < nsteps) ||
                       bad;
-        }
-        if (jend < nsteps) {  // j = nsteps - 1 >= 1: its buffers by parity (odd: the second pair)
-            _Float16* const kc = (jend & 1) ? smem + 2 * KS * TILE : smem;
-            bad = stepf(MaskTag<1>{}, kc, kc + KS * TILE, smem, smem, jend, false) || bad;
+                if (j + 1 < jend)
+                    bad = stepf(LoopTag{}, smem, smem + KS * TILE, smem + 2 * KS * TILE, smem + 3 * KS * TILE, j + 1,
+                                j + 2 < nsteps) ||
+                          bad;
+            }
+            if (jend < nsteps) {  // j = nsteps - 1 >= 1: its buffers by parity (odd: the second pair)
+                _Float16* const kc = (jend & 1) ? smem + 2 * KS * TILE : smem;
+                bad = stepf(MaskTag<1>{}, kc, kc + KS * TILE, smem, smem, jend, false) || bad;
+            }
         }
         if (__syncthreads_or(bad)) {
             // every wave restages; only the waves that saw a spike reset and recompute (the
@@ -782,6 +854,34 @@ fa2_fwd_f16_kernel(const float* __restrict__ Q, const float* __restrict__ K, con
             __builtin_amdgcn_wave_barrier();
         }
         if (h == 0 && q0 < S) LSE[(long)bh * S + q0] = st[0].m * FA2_LN2 + __logf(lt);
+    }
+}
+
+// CAUSAL, `pair` = 1: a workgroup takes TWO query blocks of its head, p and nqb - 1 - p (one
+// when they coincide), so every workgroup of a head runs the same number of key tiles
+// (nqb + 1 blocks' worth of 32 NW / 64): no round of workgroups waits on its longest block,
+// and the workgroups of an XCD keep streaming one head's K/V through its L2 together.  Grid:
+// BH * ceil(nqb / 2).  pair = 0 (grids where the pairs would leave CUs idle): one block per
+// workgroup, grid BH * nqb, a head's blocks in their natural order (issuing its last, longest
+// blocks first measured 1.5 - 6 % slower).  DESIGN.md §3 "Causal mask" has the numbers.
+template <int D, int NW, int NKB = 2, int KS = 1, bool CAUSAL = false>
+__global__ void __launch_bounds__(64 * NW)
+fa2_fwd_f16_kernel(const float* __restrict__ Q, const float* __restrict__ K, const float* __restrict__ V,
+                   float* __restrict__ O, float* __restrict__ LSE, int S, int pair) {
+    const int nqb = (S + 32 * (NW / KS) - 1) / (32 * (NW / KS));
+    const int bid = xcd_remap(blockIdx.x, gridDim.x);
+    if constexpr (CAUSAL) {
+        const int per = pair ? (nqb + 1) / 2 : nqb;  // workgroups per head
+        const int bh = bid / per, p = bid - bh * per;
+        for (int pass = 0; pass <= pair; ++pass) {
+            const int qb = pass ? nqb - 1 - p : p;
+            if (pass && qb == p) break;
+            fwd_f16_block<D, NW, NKB, KS, true>(Q, K, V, O, LSE, S, bh, qb);
+            __syncthreads();  // the next block restages the LDS buffers
+        }
+    } else {
+        const int bh = bid / nqb;
+        fwd_f16_block<D, NW, NKB, KS, false>(Q, K, V, O, LSE, S, bh, bid - bh * nqb);
     }
 }
 
@@ -1098,7 +1198,7 @@ static hipError_t fwd_f16_launch(const float* q, const float* k, const float* v,
     const long grid = (long)bh * nqb;
     if (grid <= 0 || grid > 0x7fffffffL) return hipErrorInvalidValue;
     hipLaunchKernelGGL((fa2f16::fa2_fwd_f16_kernel<D, NW, NKB, KS>), dim3((unsigned)grid), dim3(64 * NW), 0, stream, q, k,
-                       v, o, lse, S);
+                       v, o, lse, S, 0);
     return hipGetLastError();
 }
 
@@ -1245,6 +1345,35 @@ static hipError_t fwd_f16_dispatch(const float* q, const float* k, const float* 
     }
     if (nw == 2) return fwd_f16_launch<D, 2>(q, k, v, o, lse, bh, S, stream, nkb);
     return fwd_f16_launch<D, 4>(q, k, v, o, lse, bh, S, stream, nkb);
+}
+
+// Causal forward: one geometry per head dim (8 waves at D <= 64, 4 at D = 128; 64-key
+// tiles, unsplit keys) on every grid size.  No scratch, so nothing allocates or
+// synchronises.  A launch-plan override this plan cannot honour is an error.
+template <int D>
+static hipError_t fwd_f16_causal_launch(const float* q, const float* k, const float* v, float* o, float* lse, int bh,
+                                        int S, hipStream_t stream) {
+    constexpr int NW = D <= 64 ? 8 : 4;
+    if (causal_override(true, false)) return hipErrorInvalidValue;
+    const int nqb = (S + 32 * NW - 1) / (32 * NW);
+    // balanced pairs of query blocks per workgroup where their grid still covers every CU
+    const int pair = causal_pairs(bh, nqb);
+    const long grid = (long)bh * (pair ? (nqb + 1) / 2 : nqb);
+    if (grid <= 0 || grid > 0x7fffffffL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((fa2f16::fa2_fwd_f16_kernel<D, NW, 2, 1, true>), dim3((unsigned)grid), dim3(64 * NW), 0, stream,
+                       q, k, v, o, lse, S, pair);
+    return hipGetLastError();
+}
+
+hipError_t FA2_TILE_LAUNCH(launch_forward_causal)(int D, const float* q, const float* k, const float* v, float* o,
+                                                  float* lse, int bh, int S, hipStream_t stream) {
+    if (bh <= 0 || S <= 0) return hipErrorInvalidValue;
+    switch (D) {
+        case 32: return fwd_f16_causal_launch<32>(q, k, v, o, lse, bh, S, stream);
+        case 64: return fwd_f16_causal_launch<64>(q, k, v, o, lse, bh, S, stream);
+        case 128: return fwd_f16_causal_launch<128>(q, k, v, o, lse, bh, S, stream);
+        default: return hipErrorInvalidValue;
+    }
 }
 
 hipError_t FA2_TILE_LAUNCH(launch_forward)(int D, const float* q, const float* k, const float* v, float* o, float* lse, int bh,

@@ -65,6 +65,29 @@ int fa2_backward(const float* q, const float* k, const float* v, const float* o,
                  const float* lse, float* delta, float* dq, float* dk, float* dv, int batch, int heads, int seq,
                  int head_dim, int precision, void* stream);
 
+/* Masked forward and backward.  `mask`:
+ *   FA2_MASK_NONE   -- exactly fa2_forward / fa2_backward (same launch plans, same bits);
+ *   FA2_MASK_CAUSAL -- query row i attends keys j <= i (square self-attention).  LSE is the
+ *                      natural log of the sum over the allowed keys; Δ is written to `delta`
+ *                      as in fa2_backward.  FA2_FP16 and FA2_BF16 only: FA2_FP32 with a
+ *                      causal mask is FA2_E_INVALID.
+ * Any other mask value is FA2_E_INVALID (checked, like the shape, before any HIP call).
+ * The causal plans are one compiler-scheduled kernel instance per head dim (forward; dQ
+ * with Δ fused, then dK/dV) on every grid size.  Workgroups and waves skip the key tiles
+ * above the diagonal and mask only the tile that crosses it.  They use no per-stream
+ * scratch: they never allocate or synchronise and are hipGraph-capturable with no eager
+ * call before the capture.  A launch-plan override they cannot honour (FWD_HS = 1,
+ * FWD_SPLIT >= 2, FWD_KS, FWD_WAVES, FWD_NKB; DQ_HS = 1, DKDV_HS = 1, DQ_KS, DQ_WAVES,
+ * DKDV_QS, DKDV_WAVES, BWD_FUSED = 1, BWD_SPLIT >= 2) is FA2_E_INVALID at the launch, never
+ * a silent fallback.  Results are bitwise reproducible (no float atomics).
+ * fa2_version() does not change with these two: detect them by their symbols. */
+enum { FA2_MASK_NONE = 0, FA2_MASK_CAUSAL = 1 };
+int fa2_forward_masked(const float* q, const float* k, const float* v, float* o, float* lse, int batch, int heads,
+                       int seq, int head_dim, int precision, int mask, void* stream);
+int fa2_backward_masked(const float* q, const float* k, const float* v, const float* o, const float* dout,
+                        const float* lse, float* delta, float* dq, float* dk, float* dv, int batch, int heads,
+                        int seq, int head_dim, int precision, int mask, void* stream);
+
 /* The two MFMA kernels of the fp16 backward, separately (profiling/bench hooks;
  * fa2_delta + these two compute what fa2_backward with FA2_FP16 does). */
 int fa2_backward_dkdv(const float* q, const float* k, const float* v, const float* dout, const float* lse,
@@ -130,7 +153,8 @@ int fa2_shard_range(int total_heads, int shards, int index, int* first, int* cou
  * environment).  fa2_tune_set("DKDV_QS", 2) makes the next launches use that plan
  * where the shape allows it; fa2_tune_set(NULL, 0) clears every override.  Knobs:
  * FWD_HS, FWD_SPLIT, FWD_WAVES, FWD_KS, FWD_NKB, BWD_SPLIT, DKDV_HS, DKDV_WAVES, DKDV_QS, DQ_HS, DQ_WAVES,
- * DQ_KS, BWD_FUSED, BWD_FUSED_DELTA, BWD_FQS, BWD_FKS, BWD_FNW (see the launchers in
+ * DQ_KS, BWD_FUSED, BWD_FUSED_DELTA, BWD_FQS, BWD_FKS, BWD_FNW, BWD_CAUSAL_PART (timing tools:
+ * fa2_backward_masked with a causal mask launches 1 = only dQ + Δ, 2 = only dK/dV) (see the launchers in
  * kernels/; a value that forces a plan the shape cannot take is FA2_E_INVALID at the
  * launch, never a silent fallback), and
  * the test-only HOST_SHARDS_ON_DEVICE0 = 1 (fa2_*_host run every shard on device 0,

@@ -4,6 +4,13 @@ median and min per variant.  Variants are launch-plan overrides (fa2_tune_set,
 include/fa2_amd.h) or alternate library builds.
 
   python tools/kbench.py --shape 4,16,2048,64 --kernel fwd --variant FWD_WAVES=4 --variant FWD_WAVES=8
+
+--causal times the causal-mask calls (fwd, dq / dqd = dQ + Δ, dkdv, bwd, step, stepb) through
+the same loop; the pseudo-knob CAUSAL=0|1 in a --variant does it per variant, so causal and
+non-causal runs alternate in one process:
+
+  python tools/kbench.py --kernel fwd --kernel dqd --kernel dkdv --kernel step \
+      --variant FWD_HS=0,DQ_HS=0,DKDV_HS=0 --variant CAUSAL=1
 """
 import argparse
 import json
@@ -28,6 +35,8 @@ def main():
                     help="Q/K/V U[0,1) as the harness draws them, or with one late spiking key")
     ap.add_argument("--precision", choices=["fp16", "bf16", "fp32"], default="fp16",
                     help="tile precision of the fwd / bwd / stepb calls")
+    ap.add_argument("--causal", action="store_true",
+                    help="time the causal-mask calls (a variant's CAUSAL=0|1 overrides it for that variant)")
     args = ap.parse_args()
     import torch
     import fa2amd
@@ -67,6 +76,20 @@ def main():
         ev2 = torch.cuda.Event()
         ev2.record(s2)
         cur.wait_event(ev2)
+    causal = {"on": args.causal}  # set per variant (setenv)
+
+    def cbwd():
+        fa2amd.backward(q, k, v, o, do, lse, P, dq=dq, dk=dk, dv=dv, delta_buf=dl, causal=True)
+
+    # the causal calls: dQ + Δ and dK/dV alone are fa2_backward_masked under BWD_CAUSAL_PART
+    # (set around the timed loop, below)
+    causal_calls = {
+        "fwd": lambda: fa2amd.forward(q, k, v, P, out=o, lse=lse, causal=True),
+        "dq": cbwd, "dqd": cbwd, "dkdv": cbwd, "bwd": cbwd,
+        "step": lambda: (fa2amd.forward(q, k, v, P, out=o, lse=lse, causal=True), cbwd()),
+        "stepb": lambda: (fa2amd.forward(q, k, v, P, out=o, lse=lse, causal=True), cbwd()),
+    }
+    causal_part = {"dq": 1, "dqd": 1, "dkdv": 2}
     calls = {
         "fwd": lambda: fa2amd.forward(q, k, v, P, out=o, lse=lse),
         "dkdv": lambda: fa2amd.backward_dkdv(q, k, v, do, lse, dl, dk, dv),
@@ -114,18 +137,24 @@ def main():
             path, _, var = var[4:].partition(",")
             fa2amd.use_library(path)
         fa2amd.tune_set(None)
+        causal["on"] = args.causal
         for kv in filter(None, var.split(",")):
             if kv.startswith("lib="):
                 continue
             kk, vv = kv.split("=")
-            fa2amd.tune_set(kk, int(vv))
+            if kk == "CAUSAL":
+                causal["on"] = bool(int(vv))
+            else:
+                fa2amd.tune_set(kk, int(vv))
 
     res = {(kn, var): [] for kn in kernels for var in variants}
     for r in range(args.rounds):
         for var in variants:
             setenv(var)
             for kn in kernels:
-                f = calls[kn]
+                f = causal_calls[kn] if causal["on"] else calls[kn]
+                if causal["on"]:
+                    fa2amd.tune_set("BWD_CAUSAL_PART", causal_part.get(kn, 0))
                 f()
                 torch.cuda.synchronize()
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -138,7 +167,8 @@ def main():
     out = []
     for (kn, var), ts in res.items():
         med, mn = statistics.median(ts), min(ts)
-        tf = flops[kn] * B * H * S * S * D / (med * 1e-3) / 1e12
+        is_causal = args.causal if "CAUSAL=" not in var else "CAUSAL=1" in var.split(",")
+        tf = flops[kn] * (0.5 if is_causal else 1.0) * B * H * S * S * D / (med * 1e-3) / 1e12
         out.append({"kernel": kn, "variant": var or "default", "median_ms": round(med, 4), "min_ms": round(mn, 4),
                     "tflops_alg": round(tf, 1)})
         print(f"{kn:6s} {var or 'default':28s} median {med:8.4f} ms  min {mn:8.4f}  {tf:7.1f} TF(alg)")
