@@ -67,7 +67,7 @@ std::atomic<int> g_tune_n{0};
 const char* const kKnobs[] = {"FWD_HS",   "FWD_WAVES", "FWD_KS",          "FWD_NKB", "DKDV_WAVES", "DKDV_QS",
                               "DKDV_HS",  "DQ_WAVES",  "DQ_KS",           "DQ_HS",   "BWD_FUSED",  "BWD_FUSED_DELTA",
                               "BWD_FQS",  "BWD_FKS",   "BWD_FNW",         "HOST_SHARDS_ON_DEVICE0",    "HOST_CHUNKS",
-                              "FWD_SPLIT", "BWD_SPLIT", "BWD_CAUSAL_PART"};
+                              "FWD_SPLIT", "BWD_SPLIT", "BWD_CAUSAL_PART", "FWD_ROWS"};
 bool known_knob(const char* k) {
     for (const char* n : kKnobs)
         if (!strcmp(n, k)) return true;
@@ -172,6 +172,7 @@ const char* causal_override(bool fwd, bool bwd) {
     if (fwd) {
         if (tune_knob("FWD_HS", -1) == 1) return "FWD_HS";
         if (tune_knob("FWD_SPLIT", 0) >= 2) return "FWD_SPLIT";
+        if (tune_knob("FWD_ROWS", 0) == 512) return "FWD_ROWS";
         for (const char* n : {"FWD_KS", "FWD_WAVES", "FWD_NKB"})
             if (tune_knob(n, 0)) return n;
     }

@@ -12,7 +12,8 @@ Instruction semantics (lane layouts of v_mfma_f32_32x32x16_*, ds_read_b64_tr_b16
 transpose, buffer range checks) are the ones the library's compiled kernels rely on.
 Timing and hazard wait states are not modelled (the generator inserts those).
 
-  python3 asmsim.py [--D 64] [--S 256] [--bf16] [--spike]
+  python3 asmsim.py [--D 64] [--S 256] [--bf16] [--spike] [--chains 4] [--spike-rows 160:192]
+--chains 4 runs the four-chain loop (FA2_HS4_*: 512-row workgroups, D = 64).
 """
 import argparse
 import os
@@ -85,9 +86,10 @@ def tile_off(D, row, col):
 
 
 class Sim:
-    def __init__(self, D, bf16, S, Q, K, V, block=0):
+    def __init__(self, D, bf16, S, Q, K, V, block=0, chains=2):
         self.D, self.bf16, self.S = D, bf16, S
-        cfg = G.Cfg(D, bf16)
+        self.chains = chains  # 32-row chains per wave of the forward (2, or 4: 512-row workgroups)
+        cfg = G.Cfg(D, bf16, chains)
         self.cfg = cfg
         self.lds = np.zeros(cfg.lds_bytes // 4, np.uint32)  # dword-addressed
         self.Q, self.K, self.V = Q, K, V  # one head [S][D] float32
@@ -119,12 +121,14 @@ class Sim:
                 self.lds_write16(2 * (base_halves + tile_off(D, row, col)), int(h[col]))
 
     def run(self, spike_check=True):
-        """fa2_fwd_hs_kernel<D>: the C++ prologue, the asm of fa2_fwd_hs.inc, the C++ epilogue"""
+        """fa2_fwd_hs_kernel<D, NC>: the C++ prologue, the asm of fa2_fwd_hs.inc, the C++ epilogue"""
         D = self.D
         cfg = self.cfg
         TB = 64 * D
-        q0 = self.block * 256
-        self.stage(self.Q, q0, 256, 4 * TB, np.float32(LOG2E / np.sqrt(D)))
+        NC = self.chains
+        WR, ROWS = 32 * NC, 128 * NC  # query rows per wave and per workgroup
+        q0 = self.block * ROWS
+        self.stage(self.Q, q0, ROWS, 4 * TB, np.float32(LOG2E / np.sqrt(D)))
         self.stage(self.K, 0, 64, 0, np.float32(1.0))
         self.stage(self.V, 0, 64, 2 * TB, np.float32(1.0))
         lanes = np.arange(64)
@@ -136,7 +140,7 @@ class Sim:
         va = [[np.array([2 * tile_off(D, int(rt[l]) + 8 * k, 32 * b + int(ct[l])) for l in lanes]) for k in range(2)]
               for b in range(D // 32)]
         waves = []
-        text = self.asm_text()
+        text = self.asm_text(macro="FA2_HS4_ASM" if NC == 4 else "FA2_HS_ASM")
         for w in range(4):
             tid = 64 * w + lanes
             CPR = D // 8
@@ -147,8 +151,8 @@ class Sim:
                 vo.append((row * D + ch * 8) * 4)
                 if c == 0:
                     lo = 2 * np.array([row[l] * D + ((ch[l] ^ SWZ[0](D, int(row[l]))) << 3) for l in lanes])
-            ops = {"qb": 4 * TB * 2 + w * 64 * D * 2, "cnt": self.S // 64 - 1, "goff": 64 * D * 4, "flg": 0,
-                   "oa": ((w * 64 + r) * cfg.OST + 4 * h) * 4, "lo": lo, "rsk": "K", "rsv": "V"}
+            ops = {"qb": 4 * TB * 2 + w * WR * D * 2, "cnt": self.S // 64 - 1, "goff": 64 * D * 4, "flg": 0,
+                   "oa": ((w * WR + r) * cfg.OST + 4 * h) * 4, "lo": lo, "rsk": "K", "rsv": "V"}
             for t in range(len(ka)):
                 ops[f"ka{t}"] = ka[t]
             for b in range(len(va)):
@@ -169,15 +173,15 @@ class Sim:
                 break
         # C++ epilogue
         flag = any(wv.ops["flg"] for wv in waves)
-        O = np.zeros((256, D), np.float32)
-        LSE = np.zeros(256, np.float32)
+        O = np.zeros((ROWS, D), np.float32)
+        LSE = np.zeros(ROWS, np.float32)
         for w, wv in enumerate(waves):
-            for c in range(2):
+            for c in range(NC):
                 l = wv.ops[f"ol{c}"]
                 lt = l[:32] + l[32:]
                 m = wv.ops[f"om{c}"][:32]
                 for q in range(32):
-                    R = w * 64 + c * 32 + q
+                    R = w * WR + c * 32 + q
                     row = u2f(self.lds[(R * cfg.OST * 4) // 4: (R * cfg.OST * 4) // 4 + D])
                     O[R] = row / lt[q]
                     LSE[R] = m[q] * np.log(2.0) + np.log(lt[q])
@@ -625,6 +629,8 @@ def main():
     ap.add_argument("--spike", action="store_true")
     ap.add_argument("--block", type=int, default=0)
     ap.add_argument("--kernel", choices=["fwd", "dq", "dkdv"], default="fwd")
+    ap.add_argument("--chains", type=int, choices=[2, 4], default=2, help="forward: 32-row chains per wave")
+    ap.add_argument("--spike-rows", default="", help="forward: lo:hi, the query rows a late key spikes (with --spike)")
     a = ap.parse_args()
     rng = np.random.RandomState(0)
     S, D = a.S, a.D
@@ -669,12 +675,20 @@ def main():
         print(f"dQ D={D} S={S} {'bf16' if a.bf16 else 'fp16'} block {a.block}: max|ddQ| {err:.3e} (scale {scale:.2f})")
         assert err < (2e-2 if a.bf16 else 1e-2) * scale, "mismatch"
         return
-    if a.spike:
+    if a.spike and a.spike_rows:
+        # only rows lo..hi-1 see the late key: their Q rows and that key share one large column
+        lo, hi = (int(x) for x in a.spike_rows.split(":"))
+        Q[:, 0] = 0.0
+        Q[lo:hi, 0] = 30.0
+        K[:, 0] = 0.0
+        K[S - 3, 0] = 30.0
+    elif a.spike:
         K[S - 3] = 3.0
-    sim = Sim(D, a.bf16, S, Q, K, V, a.block)
-    O, LSE, flag, _ = sim.run()
-    q0 = a.block * 256
-    nq = min(256, S - q0)
+    sim = Sim(D, a.bf16, S, Q, K, V, a.block, a.chains)
+    O, LSE, flag, waves = sim.run()
+    rows = 128 * a.chains
+    q0 = a.block * rows
+    nq = min(rows, S - q0)
     s = (Q[q0:q0 + nq].astype(np.float64) @ K.T.astype(np.float64)) / np.sqrt(D)
     mx = s.max(1, keepdims=True)
     p = np.exp(s - mx)
@@ -684,6 +698,7 @@ def main():
     el = np.abs(LSE[:nq] - lse).max()
     print(f"D={D} S={S} {'bf16' if a.bf16 else 'fp16'} block {a.block}: restart flag {flag}, "
           f"max|dO| {eo:.3e}, max|dLSE| {el:.3e}")
+    print("flagged waves:", [w for w, wv in enumerate(waves) if wv.ops["flg"]])
     if not flag:
         tol = 2e-2 if a.bf16 else 1e-2
         assert eo < tol and el < tol, "mismatch"

@@ -41,6 +41,15 @@ Register map (per wave, D = head dim, NB = D/32, NTQ = D/16, CPT = D/32):
         staging      v[96 + 4 ring ...]       fp32 K then V rows of the next tile
         misc         m, l, tile partial sums, temporaries
 
+Four chains per wave (Cfg(64, bf16, nc=4), the FA2_HS4_* blocks; fa2_fwd_hs_wide_kernel, 512 query
+rows per workgroup, D = 64): the same tile staging, fragment reads and one barrier per tile
+serve four 32-row chains in eight phases (body4 has the phase table); per chain the same
+instructions in the same order as above, so O and LSE are bitwise the two-chain loop's.
+  AGPR  O[c][b]  a[16(2c+b)]  (128)   Q[c][t]  a[128 + 4(4c+t)]  (64)
+        Vf[i]    a[192 + 4i]  (32)    Kf ring  a[224 + 4r]       (32)
+  VGPR  S[c % 2][kb]  v[32(c % 2) + 16kb]  (64: only chains c, c+1 hold a live tile)
+        NM[c]  v[64 + 16c]  (64)   staging  v[128..159]   misc  v[160..191]  (m, l, T, ts, tmp x 4)
+
 Usage: python3 gen_fwd_hs.py [--check]   (--check: verify the .inc is up to date)
 """
 import os
@@ -60,8 +69,10 @@ SUM_MAX_BITS = 0x46000000  # 8192.0f: half-row tile-sum guard (FA2_TILE_SUM_MAX)
 # configuration and register map
 # ---------------------------------------------------------------------------------------
 class Cfg:
-    def __init__(self, D, bf16):
-        self.D, self.bf16 = D, bf16
+    def __init__(self, D, bf16, nc=2):
+        assert nc == 2 or (nc == 4 and D == 64), "four chains per wave: D = 64 only"
+        self.D, self.bf16, self.NC = D, bf16, nc
+        self.rows = 32 * nc * NWAVE  # query rows per workgroup
         self.NB, self.NTQ, self.CPT = D // 32, D // 16, D // 32
         self.NF = 4 * self.NB  # V fragments per tile
         self.NKF = 2 * self.NTQ  # K fragments per tile
@@ -102,6 +113,20 @@ class Cfg:
         # roundings on sums of at most 16 P; bf16 (8-bit mantissa) keeps fp32 adds, as does
         # the 'vsum' build
         self.pksum = not bf16 and "vsum" not in asmgen.ABL
+        self.kfile = "v"  # register file of the K fragment ring
+        if nc == 4:
+            # four chains (map at body4): O, Q, Vᵀ and the K ring fill the 256 AGPRs; two S
+            # slots (chain c in slot c % 2: a chain's tile dies with its PV, one phase before
+            # chain c + 2's QKᵀ), four -m splats, staging, misc
+            self.kfile = "a"
+            self.QB = 32 * self.NB * 2  # O[4][NB]
+            self.VB = self.QB + 4 * self.NTQ * 4
+            self.KB = self.VB + 4 * self.NF
+            self.nagpr = self.KB + 4 * self.ring
+            self.STG = 128
+            self.MB = self.STG + 16 * self.CPT
+            self.nvgpr = self.MB + 32
+            assert self.nagpr <= 256 and self.nvgpr <= 256 and "stamps" not in asmgen.ABL
 
     # AGPRs
     def O(self, c, b):
@@ -115,13 +140,13 @@ class Cfg:
 
     # VGPRs
     def S(self, c, kb, i=0):
-        return 32 * c + 16 * kb + i
+        return 32 * (c % 2) + 16 * kb + i
 
     def NM(self, c):
         return 64 + 16 * c
 
     def Kr(self, r):
-        return 96 + 4 * r
+        return (self.KB if self.NC == 4 else 96) + 4 * r
 
     def stg(self, tensor, cc):
         return self.STG + 8 * (tensor * self.CPT + cc)
@@ -130,16 +155,16 @@ class Cfg:
         return self.MB + c
 
     def l(self, c):
-        return self.MB + 2 + c
+        return self.MB + self.NC + c
 
     def T(self, c, k):
-        return self.MB + 4 + 4 * c + k
+        return self.MB + 2 * self.NC + 4 * c + k
 
     def ts(self, c):
-        return self.MB + 12 + c
+        return self.MB + 6 * self.NC + c
 
     def tmp(self, k):
-        return self.MB + 14 + k
+        return self.MB + 7 * self.NC + k
 
     # LDS byte offsets
     def koff(self, slot):
@@ -150,7 +175,7 @@ class Cfg:
 
     @property
     def lds_bytes(self):
-        return max(8 * self.TBB, ROWS * self.OST * 4)
+        return max((4 + 2 * self.NC) * self.TBB, self.rows * self.OST * 4)
 
     def vfrag_addr(self, i):
         b, kb, s = i // 4, (i // 2) % 2, i % 2
@@ -173,7 +198,8 @@ def mfma(cfg, dst, a, b, c, c_is_zero=False):
 def kfrag_read(cfg, f, slot, dst):
     kb, t = f // cfg.NTQ, f % cfg.NTQ
     off = cfg.koff(slot) + kb * 32 * cfg.D * 2
-    return tagged("lds", [Ins(f"ds_read_b128 {rtxt('v', dst, 4)}, %[ka{t}] offset:{off}", "dsr", [], rng("v", dst, 4))])[0]
+    kf = cfg.kfile
+    return tagged("lds", [Ins(f"ds_read_b128 {rtxt(kf, dst, 4)}, %[ka{t}] offset:{off}", "dsr", [], rng(kf, dst, 4))])[0]
 
 
 def vfrag_reads(cfg, i, slot, earliest=0):
@@ -197,7 +223,7 @@ def qk_mfmas(cfg, c, kreg, order=None):
         f = kb * cfg.NTQ + t
         cc = ("v", cfg.S(c, kb)) if kb in seeded else ("v", cfg.NM(c))
         seeded.add(kb)
-        out.append(mfma(cfg, ("v", cfg.S(c, kb)), ("v", kreg(f)), ("a", cfg.Q(c, t)), cc))
+        out.append(mfma(cfg, ("v", cfg.S(c, kb)), (cfg.kfile, kreg(f)), ("a", cfg.Q(c, t)), cc))
     return out
 
 
@@ -225,7 +251,7 @@ def qk_mfmas_zero(cfg, c, kreg):
     for kb in range(2):
         for t in range(cfg.NTQ):
             f = kb * cfg.NTQ + t
-            out.append(mfma(cfg, ("v", cfg.S(c, kb)), ("v", kreg(f)), ("a", cfg.Q(c, t)), ("v", cfg.S(c, kb)),
+            out.append(mfma(cfg, ("v", cfg.S(c, kb)), (cfg.kfile, kreg(f)), ("a", cfg.Q(c, t)), ("v", cfg.S(c, kb)),
                             c_is_zero=(t == 0)))
     return out
 
@@ -288,7 +314,7 @@ def softmax_part(cfg, c, kb, final):
         ts = cfg.ts(c)
         n0 = len(out)
         if cfg.pksum:
-            t1 = cfg.tmp(0) if c == 0 else cfg.tmp(1)
+            t1 = cfg.tmp(c)
             out.append(valu(f"v_pk_add_f16 v{T[0]}, v{T[0]}, v{T[1]}", [f"v{T[0]}", f"v{T[1]}"], [f"v{T[0]}"]))
             out.append(valu(f"v_pk_add_f16 v{T[2]}, v{T[2]}, v{T[3]}", [f"v{T[2]}", f"v{T[3]}"], [f"v{T[2]}"]))
             out.append(valu(f"v_pk_add_f16 v{T[0]}, v{T[0]}, v{T[2]}", [f"v{T[0]}", f"v{T[2]}"], [f"v{T[0]}"]))
@@ -406,7 +432,117 @@ def body(cfg, p, log):
     return seq
 
 
+def body4(cfg, p, log):
+    """four chains per wave (D = 64): one 64-key tile j with parity p in eight phases.  Chain c:
+    QKᵀ in A(c), softmax halves in B(c) and A(c+1), PV in B(c+1) (chain 3's second half and PV
+    open the next tile), so every MFMA chain runs beside another chain's softmax:
+        A0  QKᵀ(0, j)   | softmax(3, j-1) 2nd, K(j+1) convert -> slot 1-p
+        B0  PV(3, j-1)  | softmax(0, j)   1st, V(j+1) convert -> slot 1-p
+        A1  QKᵀ(1, j)   | softmax(0, j)   2nd, V(j) fragments          -> barrier
+        B1  PV(0, j)    | softmax(1, j)   1st, K(j+2) loads
+        A2  QKᵀ(2, j)   | softmax(1, j)   2nd
+        B2  PV(1, j)    | softmax(2, j)   1st, V(j+2) loads
+        A3  QKᵀ(3, j)   | softmax(2, j)   2nd
+        B3  PV(2, j)    | softmax(3, j)   1st, K(j+1) fragment prefetch
+    Only chains c and c+1 hold a live Sᵀ tile in any phase: two S slots serve four chains.
+    The barrier stands after every wave's V(j) fragment reads and K/V(j+1) LDS writes and
+    before the first read of K(j+1); the staging, fragment reads and loads are the two-chain
+    loop's, once per tile for twice the rows."""
+    q = 1 - p
+    ring = cfg.Kr
+    ph = lambda mf, streams, name: schedule_phase(cfg, mf, streams, f"{name}.{p}", log)
+    convk = staging_convert(cfg, 0, q)
+    for ins in convk:
+        ins.earliest = 2
+    vre = [r for i in range(cfg.NF) for r in vfrag_reads(cfg, i, p)]
+    pre = [kfrag_read(cfg, f, q, cfg.Kr(f)) for f in range(cfg.NKF)]
+    seq = ph(qk_mfmas(cfg, 0, ring), [softmax_part(cfg, 3, 1, True), convk], "A0")
+    seq += ph(pv_mfmas(cfg, 3), [softmax_part(cfg, 0, 0, False), staging_convert(cfg, 1, q)], "B0")
+    seq += ph(qk_mfmas(cfg, 1, ring), [softmax_part(cfg, 0, 1, True), vre], "A1")
+    seq += [Ins("s_waitcnt lgkmcnt(0)", "wait"), Ins("s_barrier", "bar")]
+    seq += ph(pv_mfmas(cfg, 0), [softmax_part(cfg, 1, 0, False), staging_loads(cfg, 0)], "B1")
+    seq += ph(qk_mfmas(cfg, 2, ring), [softmax_part(cfg, 1, 1, True)], "A2")
+    seq += ph(pv_mfmas(cfg, 1), [softmax_part(cfg, 2, 0, False), staging_loads(cfg, 1) + [goff_inc(cfg)]], "B2")
+    seq += ph(qk_mfmas(cfg, 3, ring), [softmax_part(cfg, 2, 1, True)], "A3")
+    seq += ph(pv_mfmas(cfg, 2), [softmax_part(cfg, 3, 0, False), pre], "B3")
+    return seq
+
+
+def row_max(cfg, c):
+    """row max of chain c's first tile -> m; the two lane halves hold the two key halves: xor-32 max"""
+    seq = []
+    m = cfg.m(c)
+    regs = [cfg.S(c, kb, i) for kb in range(2) for i in range(16)]
+    seq.append(valu(f"v_max3_f32 v{m}, v{regs[0]}, v{regs[1]}, v{regs[2]}", [f"v{r}" for r in regs[:3]], [f"v{m}"]))
+    k = 3
+    while k + 1 < len(regs):
+        seq.append(valu(f"v_max3_f32 v{m}, v{m}, v{regs[k]}, v{regs[k + 1]}", [f"v{m}", f"v{regs[k]}", f"v{regs[k + 1]}"],
+                        [f"v{m}"]))
+        k += 2
+    if k < len(regs):
+        seq.append(valu(f"v_max_f32 v{m}, v{m}, v{regs[k]}", [f"v{m}", f"v{regs[k]}"], [f"v{m}"]))
+    t0, t1 = cfg.tmp(0), cfg.tmp(1)
+    seq.append(valu(f"v_mov_b32 v{t0}, v{m}", [f"v{m}"], [f"v{t0}"]))
+    seq.append(valu(f"v_mov_b32 v{t1}, v{m}", [f"v{m}"], [f"v{t1}"]))
+    seq.append(valu(f"v_permlane32_swap_b32 v{t0}, v{t1}", [f"v{t0}", f"v{t1}"], [f"v{t0}", f"v{t1}"]))
+    seq.append(valu(f"v_max_f32 v{m}, v{t0}, v{t1}", [f"v{t0}", f"v{t1}"], [f"v{m}"]))
+    return seq
+
+
+def seed_and_sub(cfg, c):
+    """-m splat of chain c (the QKᵀ seed) and s - m of its first tile"""
+    seq = []
+    m, nm = cfg.m(c), cfg.NM(c)
+    seq.append(valu(f"v_sub_f32 v{nm}, 0, v{m}", [f"v{m}"], [f"v{nm}"]))
+    for i in range(1, 16):
+        seq.append(valu(f"v_mov_b32 v{nm + i}, v{nm}", [f"v{nm}"], [f"v{nm + i}"]))
+    for kb in range(2):
+        for i in range(16):
+            r = cfg.S(c, kb, i)
+            seq.append(valu(f"v_sub_f32 v{r}, v{r}, v{m}", [f"v{r}", f"v{m}"], [f"v{r}"]))
+    return seq
+
+
+def prologue4(cfg):
+    """tile 0 of the four chains one after the other through the two S slots (chain 3 stops after
+    its first softmax half, as the loop expects), then tile 1 staged and tile 2's loads issued"""
+    D, NTQ, NC = cfg.D, cfg.NTQ, cfg.NC
+    seq = [Ins("s_mov_b64 %[flg], 0", "salu", [], ["s:flg"])]
+    seq += [valu(f"v_mov_b32 v{cfg.l(c)}, 0", [], [f"v{cfg.l(c)}"]) for c in range(NC)]
+    seq += staging_loads(cfg, 0) + staging_loads(cfg, 1) + [goff_inc(cfg)]
+    for t in range(NTQ):
+        seq.append(valu(f"v_add_u32 v{t}, %[qb], %[ka{t}]", [], [f"v{t}"]))
+    for c in range(NC):
+        for t in range(NTQ):
+            d = cfg.Q(c, t)
+            seq.append(Ins(f"ds_read_b128 {rtxt('a', d, 4)}, v{t} offset:{c * 32 * D * 2}", "dsr", R([f"v{t}"]),
+                           rng("a", d, 4)))
+    for f in range(cfg.NKF):
+        seq.append(kfrag_read(cfg, f, 0, cfg.Kr(f)))
+    for i in range(cfg.NF):
+        seq += vfrag_reads(cfg, i, 0)
+    for c in range(NC):
+        seq += qk_mfmas_zero(cfg, c, cfg.Kr)
+        seq += row_max(cfg, c) + seed_and_sub(cfg, c)
+        seq += softmax_part(cfg, c, 0, False)
+        if c == NC - 1:
+            for b in range(cfg.NB):
+                for i in range(16):
+                    r = cfg.O(c, b) + i
+                    seq.append(valu(f"v_accvgpr_write_b32 a{r}, 0", [], [f"a{r}"]))
+        else:
+            seq += softmax_part(cfg, c, 1, True)
+            seq += pv_mfmas(cfg, c, first=True)
+    seq += staging_convert(cfg, 0, 1) + staging_convert(cfg, 1, 1)
+    seq += staging_loads(cfg, 0) + staging_loads(cfg, 1) + [goff_inc(cfg)]
+    seq += [Ins("s_waitcnt lgkmcnt(0)", "wait"), Ins("s_barrier", "bar")]
+    seq += [kfrag_read(cfg, f, 1, cfg.Kr(f)) for f in range(cfg.NKF)]
+    return seq
+
+
 def prologue(cfg):
+    if cfg.NC == 4:
+        return prologue4(cfg)
     D, NTQ, NKF = cfg.D, cfg.NTQ, cfg.NKF
     seq = [Ins("s_mov_b32 s98, 0", "salu", [], ["s98"])] if "stamps" in asmgen.ABL else []
     seq += stamp(cfg.SV)
@@ -429,33 +565,10 @@ def prologue(cfg):
         seq.append(kfrag_read(cfg, f, 0, kreg0(f)))
     # Sᵀ of tile 0 for both chains (no -m seed yet)
     seq += qk_mfmas_zero(cfg, 0, kreg0) + qk_mfmas_zero(cfg, 1, kreg0)
-    # row max per chain -> m; the two lane halves hold the two key halves: xor-32 max
     for c in range(2):
-        m = cfg.m(c)
-        regs = [cfg.S(c, kb, i) for kb in range(2) for i in range(16)]
-        seq.append(valu(f"v_max3_f32 v{m}, v{regs[0]}, v{regs[1]}, v{regs[2]}", [f"v{r}" for r in regs[:3]], [f"v{m}"]))
-        k = 3
-        while k + 1 < len(regs):
-            seq.append(valu(f"v_max3_f32 v{m}, v{m}, v{regs[k]}, v{regs[k + 1]}", [f"v{m}", f"v{regs[k]}", f"v{regs[k + 1]}"],
-                            [f"v{m}"]))
-            k += 2
-        if k < len(regs):
-            seq.append(valu(f"v_max_f32 v{m}, v{m}, v{regs[k]}", [f"v{m}", f"v{regs[k]}"], [f"v{m}"]))
-        t0, t1 = cfg.tmp(0), cfg.tmp(1)
-        seq.append(valu(f"v_mov_b32 v{t0}, v{m}", [f"v{m}"], [f"v{t0}"]))
-        seq.append(valu(f"v_mov_b32 v{t1}, v{m}", [f"v{m}"], [f"v{t1}"]))
-        seq.append(valu(f"v_permlane32_swap_b32 v{t0}, v{t1}", [f"v{t0}", f"v{t1}"], [f"v{t0}", f"v{t1}"]))
-        seq.append(valu(f"v_max_f32 v{m}, v{t0}, v{t1}", [f"v{t0}", f"v{t1}"], [f"v{m}"]))
-    # -m splats (the QKᵀ seeds) and s - m of tile 0
+        seq += row_max(cfg, c)
     for c in range(2):
-        m, nm = cfg.m(c), cfg.NM(c)
-        seq.append(valu(f"v_sub_f32 v{nm}, 0, v{m}", [f"v{m}"], [f"v{nm}"]))
-        for i in range(1, 16):
-            seq.append(valu(f"v_mov_b32 v{nm + i}, v{nm}", [f"v{nm}"], [f"v{nm + i}"]))
-        for kb in range(2):
-            for i in range(16):
-                r = cfg.S(c, kb, i)
-                seq.append(valu(f"v_sub_f32 v{r}, v{r}, v{m}", [f"v{r}", f"v{m}"], [f"v{r}"]))
+        seq += seed_and_sub(cfg, c)
     seq += softmax_part(cfg, 0, 0, False) + softmax_part(cfg, 0, 1, True) + softmax_part(cfg, 1, 0, False)
     # V(0) fragments, O[B] = 0, PV of chain A (tile 0)
     for i in range(cfg.NF):
@@ -478,17 +591,17 @@ def epilogue(cfg):
     D = cfg.D
     seq = [Ins("s_waitcnt vmcnt(0) lgkmcnt(0)", "wait")]
     seq += stamp(cfg.SV)
-    seq += softmax_part(cfg, 1, 1, True)
-    seq += pv_mfmas(cfg, 1)
+    seq += softmax_part(cfg, cfg.NC - 1, 1, True)
+    seq += pv_mfmas(cfg, cfg.NC - 1)
     # every wave is done with the tile slots before the O stage overwrites them
     seq.append(Ins("s_barrier", "bar"))
-    for c in range(2):
+    for c in range(cfg.NC):
         for b in range(cfg.NB):
             for g in range(4):
                 r = cfg.O(c, b) + 4 * g
                 off = (c * 32 * cfg.OST + 32 * b + 8 * g) * 4
                 seq.append(Ins(f"ds_write_b128 %[oa], {rtxt('a', r, 4)} offset:{off}", "dsw", R(rng("a", r, 4)), []))
-    for c in range(2):
+    for c in range(cfg.NC):
         seq.append(valu(f"v_mov_b32 %[om{c}], v{cfg.m(c)}", [f"v{cfg.m(c)}"], []))
         seq.append(valu(f"v_mov_b32 %[ol{c}], v{cfg.l(c)}", [f"v{cfg.l(c)}"], []))
     if "stamps" in asmgen.ABL:
@@ -513,11 +626,12 @@ def epilogue(cfg):
 # whole program
 # ---------------------------------------------------------------------------------------
 def build(cfg):
-    log = [f"D={cfg.D} {'bf16' if cfg.bf16 else 'fp16'}: {cfg.nvgpr} VGPRs + {cfg.nagpr} AGPRs in asm, "
+    log = [f"D={cfg.D} {'bf16' if cfg.bf16 else 'fp16'}{', four chains' if cfg.NC == 4 else ''}: {cfg.nvgpr} VGPRs + {cfg.nagpr} AGPRs in asm, "
            f"LDS {cfg.lds_bytes} B"]
     pro = prologue(cfg)
-    b1 = ablate(body(cfg, 1, log))
-    b0 = ablate(body(cfg, 0, log))
+    body_fn = body4 if cfg.NC == 4 else body
+    b1 = ablate(body_fn(cfg, 1, log))
+    b0 = ablate(body_fn(cfg, 0, log))
     epi = epilogue(cfg)
     empty = ((), ())
     pro, st_p = insert_waits(pro, empty)
@@ -550,8 +664,11 @@ def build(cfg):
 
 
 def operands(cfg):
-    outs = ['[om0] "=&v"(hs_m0)', '[om1] "=&v"(hs_m1)', '[ol0] "=&v"(hs_l0)', '[ol1] "=&v"(hs_l1)',
-            '[flg] "=&s"(hs_flag)', '[cnt] "+s"(hs_cnt)', '[goff] "+s"(hs_goff)']
+    if cfg.NC == 4:
+        outs = [f'[o{x}{c}] "=&v"(hs_{x}[{c}])' for x in "ml" for c in range(4)]
+    else:
+        outs = ['[om0] "=&v"(hs_m0)', '[om1] "=&v"(hs_m1)', '[ol0] "=&v"(hs_l0)', '[ol1] "=&v"(hs_l1)']
+    outs += ['[flg] "=&s"(hs_flag)', '[cnt] "+s"(hs_cnt)', '[goff] "+s"(hs_goff)']
     ins = [f'[ka{t}] "v"(hs_ka[{t}])' for t in range(cfg.NTQ)]
     ins += [f'[va{b}_{k}] "v"(hs_va[{b}][{k}])' for b in range(cfg.NB) for k in range(2)]
     ins += [f'[vo{c}] "v"(hs_vo[{c}])' for c in range(cfg.CPT)]
@@ -585,6 +702,22 @@ def emit():
         out.append(f"#define FA2_HS_CLOBBERS_D{D} " + ", ".join(c))
         out.append(f"#define FA2_HS_LDS_D{D} {cfg.lds_bytes}")
         out.append("")
+    # four chains per wave (512-row workgroups), D = 64
+    for bf16 in (False, True):
+        cfg = Cfg(64, bf16, nc=4)
+        lines, log = build(cfg)
+        logs += log
+        out.append(f"#define FA2_HS4_ASM_D64_{'BF16' if bf16 else 'F16'} \\")
+        out += [f'    "{ln}\\n\\t" \\' for ln in lines]
+        out.append('    ""')
+        out.append("")
+    cfg = Cfg(64, False, nc=4)
+    o, i, c = operands(cfg)
+    out.append("#define FA2_HS4_OUTPUTS_D64 " + ", ".join(o))
+    out.append("#define FA2_HS4_INPUTS_D64 " + ", ".join(i))
+    out.append("#define FA2_HS4_CLOBBERS_D64 " + ", ".join(c))
+    out.append(f"#define FA2_HS4_LDS_D64 {cfg.lds_bytes}")
+    out.append("")
     out = ["// " + ln for ln in logs] + out
     text = "\n".join(out) + "\n"
     path = os.path.join(here, "..", "kernels", "fa2_fwd_hs.inc")

@@ -927,27 +927,34 @@ __device__ __forceinline__ void fwd_store_part(const FwdState<D>& st, float* par
     }
 }
 
-template <int D>
-__global__ void __launch_bounds__(256, 1)
-fa2_fwd_hs_kernel(const float* __restrict__ Q, const float* __restrict__ K, const float* __restrict__ V,
-                  float* __restrict__ O, float* __restrict__ LSE, int S, int P, float* __restrict__ part) {
-    static_assert(D == 64 || D == 128, "hand-scheduled forward: D = 64 or 128");
+// NC = 32-row chains per wave: 2 (256-row workgroups, D = 64 / 128) or 4 (512-row workgroups,
+// D = 64: the FA2_HS4 loop -- the K/V staging, fragment reads and barrier of a tile serve
+// twice the rows; per row the same instructions in the same order, so O and LSE are bitwise
+// those of NC = 2 wherever no wave restarts).
+template <int D, int NC>
+__device__ __forceinline__ void fwd_hs_body(const float* __restrict__ Q, const float* __restrict__ K,
+                                            const float* __restrict__ V, float* __restrict__ O,
+                                            float* __restrict__ LSE, int S, int P, float* __restrict__ part) {
+    static_assert((NC == 2 && (D == 64 || D == 128)) || (NC == 4 && D == 64),
+                  "hand-scheduled forward: D = 64 or 128; four chains at D = 64 only");
     constexpr int KT = 64, TB = KT * D;  // halves per tile image
     constexpr int OST = D + 4;           // O stage row stride (floats), as in the generator
-    constexpr int LDSB = D == 64 ? FA2_HS_LDS_D64 : FA2_HS_LDS_D128;
+    constexpr int WR = 32 * NC, ROWS = 4 * WR;  // query rows per wave and per workgroup
+    constexpr int LDSB = NC == 4 ? FA2_HS4_LDS_D64 : D == 64 ? FA2_HS_LDS_D64 : FA2_HS_LDS_D128;
+    static_assert(LDSB >= (4 * TB + ROWS * D) * 2 && LDSB >= ROWS * OST * 4, "tile rings + Q block, O stage");
     __shared__ __attribute__((aligned(16))) _Float16 smem[LDSB / 2];
-    __shared__ float invl[256];
+    __shared__ float invl[ROWS];
 
     const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, h = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int nqb = (S + 255) / 256;
+    const int nqb = (S + ROWS - 1) / ROWS;
     // workgroup -> (head, key chunk, query block): the query blocks of one chunk are
     // consecutive, so after the XCD remap they share one L2's copy of the chunk's K/V
     const int bid = xcd_remap(blockIdx.x, gridDim.x);
     const int qb = bid % nqb, bc = bid / nqb;
     const int bh = bc / P, kc = bc - bh * P;
     const long base = (long)bh * S * D;
-    const int qrow0 = qb * 256;
+    const int qrow0 = qb * ROWS;
     const int L = S / P;            // keys of this workgroup's chunk (S itself when P = 1)
     const long kbase = base + (long)kc * L * D;
     // P > 1: this chunk's partial rows (see fwd_store_part)
@@ -955,8 +962,8 @@ fa2_fwd_hs_kernel(const float* __restrict__ Q, const float* __restrict__ K, cons
     float* part_o = P > 1 ? part + prow * D : nullptr;
     float* part_ml = P > 1 ? part + (long)gridDim.x / nqb * S * D + prow * 2 : nullptr;
 
-    // Q block (256 rows, scaled by log2(e)/sqrt(D)) -> LDS [4TB, 8TB) halves; K(0), V(0)
-    // -> slot 0 of the K and V rings ([0, TB) and [2TB, 3TB))
+    // Q block (ROWS rows, scaled by log2(e)/sqrt(D); rows past S read as zeros) -> LDS from
+    // 4TB halves on; K(0), V(0) -> slot 0 of the K and V rings ([0, TB) and [2TB, 3TB))
     TileStager<D, KT, 256> ks, vs;
     ks.init(K + kbase, L, tid);
     vs.init(V + kbase, L, tid);
@@ -967,6 +974,11 @@ fa2_fwd_hs_kernel(const float* __restrict__ Q, const float* __restrict__ K, cons
         ks.load(0);
         vs.load(0);
         qst.store(smem + 4 * TB, FA2_LOG2E / __builtin_sqrtf((float)D), tid);
+        if constexpr (NC == 4) {
+            // the block's second 256 rows (the swizzle reads row bits 0..3 only)
+            qst.load(qrow0 + 256);
+            qst.store(smem + 4 * TB + 256 * D, FA2_LOG2E / __builtin_sqrtf((float)D), tid);
+        }
         ks.store(smem, 1.f, tid);
         vs.store(smem + 2 * TB, 1.f, tid);
     }
@@ -985,103 +997,132 @@ fa2_fwd_hs_kernel(const float* __restrict__ Q, const float* __restrict__ K, cons
 #pragma unroll
     for (int c = 0; c < D / 32; ++c) hs_vo[c] = ks.voff[c];
     const int hs_lo = ks.loff[0] * 2;
-    const int hs_oa = ((wave * 64 + r) * OST + 4 * h) * 4;
+    const int hs_oa = ((wave * WR + r) * OST + 4 * h) * 4;
     const __amdgpu_buffer_rsrc_t hs_rsk = ks.rs, hs_rsv = vs.rs;
-    const int hs_qb = __builtin_amdgcn_readfirstlane(4 * TB * 2 + wave * 64 * D * 2);
+    const int hs_qb = __builtin_amdgcn_readfirstlane(4 * TB * 2 + wave * WR * D * 2);
     int hs_cnt = __builtin_amdgcn_readfirstlane(L / KT - 1);
     int hs_goff = __builtin_amdgcn_readfirstlane(KT * D * 4);
-    float hs_m0, hs_m1, hs_l0, hs_l1;
+    float hs_m[NC], hs_l[NC];  // per chain: m (log2 units) and the lane half's row sum
     unsigned long long hs_flag;
-    if constexpr (D == 64) {
+    if constexpr (NC == 4) {
 #ifdef FA2_TILE_BF16
-        asm volatile(FA2_HS_ASM_D64_BF16 : FA2_HS_OUTPUTS_D64 : FA2_HS_INPUTS_D64 : FA2_HS_CLOBBERS_D64);
+        asm volatile(FA2_HS4_ASM_D64_BF16 : FA2_HS4_OUTPUTS_D64 : FA2_HS4_INPUTS_D64 : FA2_HS4_CLOBBERS_D64);
 #else
-        asm volatile(FA2_HS_ASM_D64_F16 : FA2_HS_OUTPUTS_D64 : FA2_HS_INPUTS_D64 : FA2_HS_CLOBBERS_D64);
+        asm volatile(FA2_HS4_ASM_D64_F16 : FA2_HS4_OUTPUTS_D64 : FA2_HS4_INPUTS_D64 : FA2_HS4_CLOBBERS_D64);
 #endif
     } else {
+        float hs_m0, hs_m1, hs_l0, hs_l1;
+        if constexpr (D == 64) {
 #ifdef FA2_TILE_BF16
-        asm volatile(FA2_HS_ASM_D128_BF16 : FA2_HS_OUTPUTS_D128 : FA2_HS_INPUTS_D128 : FA2_HS_CLOBBERS_D128);
+            asm volatile(FA2_HS_ASM_D64_BF16 : FA2_HS_OUTPUTS_D64 : FA2_HS_INPUTS_D64 : FA2_HS_CLOBBERS_D64);
 #else
-        asm volatile(FA2_HS_ASM_D128_F16 : FA2_HS_OUTPUTS_D128 : FA2_HS_INPUTS_D128 : FA2_HS_CLOBBERS_D128);
+            asm volatile(FA2_HS_ASM_D64_F16 : FA2_HS_OUTPUTS_D64 : FA2_HS_INPUTS_D64 : FA2_HS_CLOBBERS_D64);
 #endif
+        } else {
+#ifdef FA2_TILE_BF16
+            asm volatile(FA2_HS_ASM_D128_BF16 : FA2_HS_OUTPUTS_D128 : FA2_HS_INPUTS_D128 : FA2_HS_CLOBBERS_D128);
+#else
+            asm volatile(FA2_HS_ASM_D128_F16 : FA2_HS_OUTPUTS_D128 : FA2_HS_INPUTS_D128 : FA2_HS_CLOBBERS_D128);
+#endif
+        }
+        hs_m[0] = hs_m0, hs_m[1] = hs_m1, hs_l[0] = hs_l0, hs_l[1] = hs_l1;
     }
 
     // hs_flag is a scalar (wave-uniform): this wave saw a half-row sum out of range
     const bool wave_bad = hs_flag != 0;
     const bool any_bad = __syncthreads_or(wave_bad);
+    const int q0 = qrow0 + wave * WR + r;  // this lane's row of chain 0; chain c: + 32 c
     if (!wave_bad && P > 1) {
         // a key chunk's partial: the unnormalised O rows from the stage, (m, l) per row
-        const float lt0 = xor32_sum(hs_l0), lt1 = xor32_sum(hs_l1);
-        const int q0 = qrow0 + wave * 64 + r;
-        if (h == 0) {
-            if (q0 < S) *reinterpret_cast<float2*>(part_ml + 2L * q0) = make_float2(hs_m0, lt0);
-            if (q0 + 32 < S) *reinterpret_cast<float2*>(part_ml + 2L * (q0 + 32)) = make_float2(hs_m1, lt1);
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            const float lt = xor32_sum(hs_l[c]);
+            if (h == 0 && q0 + 32 * c < S)
+                *reinterpret_cast<float2*>(part_ml + 2L * (q0 + 32 * c)) = make_float2(hs_m[c], lt);
         }
         constexpr int LPR = D / 4, RPI = 64 / LPR;
         const float* os = reinterpret_cast<const float*>(smem);
 #pragma unroll 4
-        for (int rr = 0; rr < 64; rr += RPI) {
-            const int row = wave * 64 + rr + lane / LPR, c4 = (lane % LPR) * 4;
+        for (int rr = 0; rr < WR; rr += RPI) {
+            const int row = wave * WR + rr + lane / LPR, c4 = (lane % LPR) * 4;
             const f32x4 v = *reinterpret_cast<const f32x4*>(os + row * OST + c4);
             if (qrow0 + row < S) *reinterpret_cast<f32x4*>(part_o + (long)(qrow0 + row) * D + c4) = v;
         }
     } else if (!wave_bad) {
-        // O rows [wave*64 + c*32 + q][OST] (unnormalised) are in the stage; l is per lane
+        // O rows [wave*WR + c*32 + q][OST] (unnormalised) are in the stage; l is per lane
         // half: the xor-32 sum is the row's total
-        const float lt0 = xor32_sum(hs_l0), lt1 = xor32_sum(hs_l1);
-        if (h == 0) {
-            invl[wave * 64 + r] = 1.f / lt0;
-            invl[wave * 64 + 32 + r] = 1.f / lt1;
-            const int q0 = qrow0 + wave * 64 + r;
-            if (q0 < S) LSE[(long)bh * S + q0] = hs_m0 * FA2_LN2 + __logf(lt0);
-            if (q0 + 32 < S) LSE[(long)bh * S + q0 + 32] = hs_m1 * FA2_LN2 + __logf(lt1);
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            const float lt = xor32_sum(hs_l[c]);
+            if (h == 0) {
+                invl[wave * WR + 32 * c + r] = 1.f / lt;
+                if (q0 + 32 * c < S) LSE[(long)bh * S + q0 + 32 * c] = hs_m[c] * FA2_LN2 + __logf(lt);
+            }
         }
         __builtin_amdgcn_wave_barrier();
         // whole rows: D/4 lanes per row, 16-B pieces
         constexpr int LPR = D / 4, RPI = 64 / LPR;
         const float* os = reinterpret_cast<const float*>(smem);
 #pragma unroll 4
-        for (int rr = 0; rr < 64; rr += RPI) {
-            const int row = wave * 64 + rr + lane / LPR, c4 = (lane % LPR) * 4;
+        for (int rr = 0; rr < WR; rr += RPI) {
+            const int row = wave * WR + rr + lane / LPR, c4 = (lane % LPR) * 4;
             const f32x4 v = *reinterpret_cast<const f32x4*>(os + row * OST + c4) * invl[row];
             if (qrow0 + row < S) *reinterpret_cast<f32x4*>(O + base + (long)(qrow0 + row) * D + c4) = v;
         }
     }
     if (!any_bad) return;
     // Robust path (a late score spike in some wave's rows): only the flagged waves
-    // recompute, both chains in ONE pass over the head's K/V with the rescaling loop
-    // (first tile sets m, later tiles move it when their sums leave range); the other
-    // waves have stored their rows above and only help stage the tiles.  The barrier
-    // keeps the restaging from overwriting an O stage another wave still reads.
+    // recompute, two chains per pass over the head's K/V with the rescaling loop (first
+    // tile sets m, later tiles move it when their sums leave range; NC = 4: two passes,
+    // four 32-row states do not fit beside the score tiles); the other waves have stored
+    // their rows above and only help stage the tiles.  The barrier keeps the restaging
+    // from overwriting an O stage another wave still reads.
     __syncthreads();
-    FwdState<D> st[2];
-    const int q = qrow0 + wave * 64 + r;
-    if (wave_bad) {
-        fwd_init<D>(st[0], Q, base, q, S, h);
-        fwd_init<D>(st[1], Q, base, q + 32, S, h);
-    }
     const int ntiles = L / KT;
 #pragma unroll 1
-    for (int j = 0; j < ntiles; ++j) {
-        ks.load(j * KT);
-        vs.load(j * KT);
-        if (j) __syncthreads();  // the previous tile's reads are done
-        ks.store(smem, 1.f, tid);
-        vs.store(smem + TB, 1.f, tid);
-        __syncthreads();
+    for (int pass = 0; pass < NC / 2; ++pass) {
+        FwdState<D> st[2];
+        const int q = q0 + 64 * pass;
         if (wave_bad) {
-            f32x16 sacc[2][2];
-            fwd_qk<D, 2, 2, true>(sacc, st, smem, fo);
-            fwd_softmax_pv<D, 2, false, 2, true>(st, sacc, smem + TB, fo, j * KT, L, h, j == 0);
+            fwd_init<D>(st[0], Q, base, q, S, h);
+            fwd_init<D>(st[1], Q, base, q + 32, S, h);
+        }
+#pragma unroll 1
+        for (int j = 0; j < ntiles; ++j) {
+            ks.load(j * KT);
+            vs.load(j * KT);
+            if (j || pass) __syncthreads();  // the previous tile's reads are done
+            ks.store(smem, 1.f, tid);
+            vs.store(smem + TB, 1.f, tid);
+            __syncthreads();
+            if (wave_bad) {
+                f32x16 sacc[2][2];
+                fwd_qk<D, 2, 2, true>(sacc, st, smem, fo);
+                fwd_softmax_pv<D, 2, false, 2, true>(st, sacc, smem + TB, fo, j * KT, L, h, j == 0);
+            }
+        }
+        if (wave_bad && P > 1) {
+            fwd_store_part<D>(st[0], part_o, part_ml, q, S, h);
+            fwd_store_part<D>(st[1], part_o, part_ml, q + 32, S, h);
+        } else if (wave_bad) {
+            fwd_store<D>(st[0], O, LSE, base, (long)bh * S, q, S, h);
+            fwd_store<D>(st[1], O, LSE, base, (long)bh * S, q + 32, S, h);
         }
     }
-    if (wave_bad && P > 1) {
-        fwd_store_part<D>(st[0], part_o, part_ml, q, S, h);
-        fwd_store_part<D>(st[1], part_o, part_ml, q + 32, S, h);
-    } else if (wave_bad) {
-        fwd_store<D>(st[0], O, LSE, base, (long)bh * S, q, S, h);
-        fwd_store<D>(st[1], O, LSE, base, (long)bh * S, q + 32, S, h);
-    }
+}
+
+template <int D>
+__global__ void __launch_bounds__(256, 1)
+fa2_fwd_hs_kernel(const float* __restrict__ Q, const float* __restrict__ K, const float* __restrict__ V,
+                  float* __restrict__ O, float* __restrict__ LSE, int S, int P, float* __restrict__ part) {
+    fwd_hs_body<D, 2>(Q, K, V, O, LSE, S, P, part);
+}
+
+// 512-row workgroups (four chains per wave), D = 64, unsplit (P = 1)
+__global__ void __launch_bounds__(256, 1)
+fa2_fwd_hs_wide_kernel(const float* __restrict__ Q, const float* __restrict__ K, const float* __restrict__ V,
+                       float* __restrict__ O, float* __restrict__ LSE, int S) {
+    fwd_hs_body<64, 4>(Q, K, V, O, LSE, S, 1, nullptr);
 }
 
 // Merge of the P key-chunk partials of fa2_fwd_hs_kernel (layout at fwd_store_part), in
@@ -1219,6 +1260,33 @@ static hipError_t fwd_hs_launch(const float* q, const float* k, const float* v, 
     return hipGetLastError();
 }
 
+// 512-row workgroups (fa2_fwd_hs_wide_kernel): D = 64, S % 64 == 0, S >= 128, unsplit
+static hipError_t fwd_hs_wide_launch(const float* q, const float* k, const float* v, float* o, float* lse, int bh,
+                                     int S, hipStream_t stream) {
+    if (S % 64 || S < 128) return hipErrorInvalidValue;
+    const long grid = (long)bh * ((S + 511) / 512);
+    if (grid <= 0 || grid > 0x7fffffffL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(fa2f16::fa2_fwd_hs_wide_kernel, dim3((unsigned)grid), dim3(256), 0, stream, q, k, v, o, lse, S);
+    return hipGetLastError();
+}
+
+// Rows per workgroup of the hand-scheduled D = 64 forward where it runs unsplit: 512 when the
+// 512-row grid g5 still holds one workgroup per CU, adds no empty rows (ceil(S / 256) even)
+// and, up to two rounds of workgroups, leaves no longer tail than the 256-row grid g2 (a
+// 512-row round lasts 1.8 rounds of 256 rows: 2 ceil(g5 / CUs) == ceil(g2 / CUs)); past two
+// rounds it won at every grid measured.  In-process, forward, B1_H*_S2048 on 256 CUs
+// (profiles/wide/grid_H*.log), 256 -> 512 rows by g5 / CUs: 1.0 75.3 -> 67.5 us, 1.25 107.4
+// -> 116.4 (stays 256), 1.5 115.6 -> 120.8 (stays 256), 1.75 142.0 -> 125.6, 2.25 198.2 ->
+// 186.4, 2.5 208.4 -> 189.8, 3.25 281.6 -> 255.8, 4.25 362.4 -> 320.8, 5.25 444.1 -> 386.8;
+// an odd count of 256-row blocks (B4_H32_S2304) 204.1 -> 200.9, inside the spread: stays 256.
+// B2_H8_S4096 (128 workgroups of 512 rows) keeps the 256-row plan.
+static bool fwd_rows_auto_512(int bh, int S) {
+    const long ncu = cu_count();
+    const long n2 = (S + 255) / 256, g2 = bh * n2, g5 = bh * ((S + 511) / 512);
+    if (n2 % 2 || g5 < ncu) return false;
+    return g5 > 2 * ncu || 2 * ((g5 + ncu - 1) / ncu) == (g2 + ncu - 1) / ncu;
+}
+
 // Key chunks per head for a grid of `g` 256-row workgroups that leaves CUs idle: the
 // most chunks (a power of two, at most 4) that keep the grid within one workgroup per
 // CU and chunks of at least 1024 keys (D = 64) / 256 keys (D = 128), for heads of at
@@ -1254,11 +1322,17 @@ static hipError_t fwd_f16_dispatch(const float* q, const float* k, const float* 
         // (Its 16x16x32 form lost in r05: C3 +3.6 %, B2_H8_S4096 +4.7 %, C4 +0.8 %, in-process,
         // profiles/r05/fwd16/: the forward is issue-bound and 16x16x32 halves the issue room
         // per MFMA cycle)
-        const int hs = tune_knob("FWD_HS", -1);
+        // FWD_ROWS (tests and tools): query rows per workgroup of the unsplit hand-scheduled
+        // plan, 256 | 512 (0 = auto, fwd_rows_auto_512); 512 is D = 64 only and an error
+        // where the plan cannot take it (shape, other plan knobs, FWD_HS = 0, FWD_SPLIT >= 2)
+        const int hs = tune_knob("FWD_HS", -1), rows = tune_knob("FWD_ROWS", 0);
+        if (rows != 0 && rows != 256 && rows != 512) return hipErrorInvalidValue;
         const bool fits = S % 64 == 0 && S >= 128;
         const bool forced_other = tune_knob("FWD_WAVES", 0) || tune_knob("FWD_KS", 0) || tune_knob("FWD_NKB", 0);
         // a forced FWD_HS the plan cannot take (shape, or other plan knobs) is an error
         if (hs == 1 && (!fits || forced_other)) return hipErrorInvalidValue;
+        if (rows == 512 && (D != 64 || !fits || forced_other || hs == 0 || tune_knob("FWD_SPLIT", 0) >= 2))
+            return hipErrorInvalidValue;
         const long g = (long)bh * ((S + 255) / 256);
         // FWD_SPLIT (tests and tools): P >= 2 forces P key chunks per head on the
         // hand-scheduled kernel (an error where it cannot serve: shape, other plan knobs,
@@ -1269,17 +1343,22 @@ static hipError_t fwd_f16_dispatch(const float* q, const float* k, const float* 
         if (split >= 2 && (!fits || forced_other || hs == 0 || S % (64 * split) || S / split < 128))
             return hipErrorInvalidValue;
         int P = split >= 2 ? split : 1;
-        if (split == 0 && fits && hs < 0 && !forced_other && g < cu_count()) P = fwd_split_auto(D, g, S);
+        if (split == 0 && fits && hs < 0 && rows != 512 && !forced_other && g < cu_count()) P = fwd_split_auto(D, g, S);
         if (P > 1) {
             float* part = static_cast<float*>(stream_scratch(stream, sizeof(float) * P * (size_t)bh * S * (D + 2)));
             if (part) return fwd_hs_launch<D>(q, k, v, o, lse, bh, S, stream, P, part);
             if (split >= 2) return hipErrorInvalidValue;
         }
-        if (fits && (hs == 1 || (hs < 0 && !forced_other && g >= cu_count())))
+        if (fits && (hs == 1 || rows == 512 || (hs < 0 && !forced_other && g >= cu_count()))) {
+            if constexpr (D == 64)
+                if (rows == 512 || (rows == 0 && fwd_rows_auto_512(bh, S)))
+                    return fwd_hs_wide_launch(q, k, v, o, lse, bh, S, stream);
             return fwd_hs_launch<D>(q, k, v, o, lse, bh, S, stream);
+        }
     } else {
         // no hand-scheduled kernel at this D
-        if (tune_knob("FWD_HS", -1) == 1 || tune_knob("FWD_SPLIT", 0) >= 2) return hipErrorInvalidValue;
+        if (tune_knob("FWD_HS", -1) == 1 || tune_knob("FWD_SPLIT", 0) >= 2 || tune_knob("FWD_ROWS", 0) == 512)
+            return hipErrorInvalidValue;
     }
     // 8 waves (2 per SIMD) where the registers allow it; D = 128 runs 4 waves of
     // ~400 VGPRs (8 would spill and exceed the LDS budget with the Q stages)

@@ -77,7 +77,7 @@ int fa2_backward(const float* q, const float* k, const float* v, const float* o,
  * above the diagonal and mask only the tile that crosses it.  They use no per-stream
  * scratch: they never allocate or synchronise and are hipGraph-capturable with no eager
  * call before the capture.  A launch-plan override they cannot honour (FWD_HS = 1,
- * FWD_SPLIT >= 2, FWD_KS, FWD_WAVES, FWD_NKB; DQ_HS = 1, DKDV_HS = 1, DQ_KS, DQ_WAVES,
+ * FWD_SPLIT >= 2, FWD_ROWS = 512, FWD_KS, FWD_WAVES, FWD_NKB; DQ_HS = 1, DKDV_HS = 1, DQ_KS, DQ_WAVES,
  * DKDV_QS, DKDV_WAVES, BWD_FUSED = 1, BWD_SPLIT >= 2) is FA2_E_INVALID at the launch, never
  * a silent fallback.  Results are bitwise reproducible (no float atomics).
  * fa2_version() does not change with these two: detect them by their symbols. */
@@ -152,11 +152,18 @@ int fa2_shard_range(int total_heads, int shards, int index, int* first, int* cou
 /* Launch-plan override (tests and tuning tools only; nothing is read from the
  * environment).  fa2_tune_set("DKDV_QS", 2) makes the next launches use that plan
  * where the shape allows it; fa2_tune_set(NULL, 0) clears every override.  Knobs:
- * FWD_HS, FWD_SPLIT, FWD_WAVES, FWD_KS, FWD_NKB, BWD_SPLIT, DKDV_HS, DKDV_WAVES, DKDV_QS, DQ_HS, DQ_WAVES,
+ * FWD_HS, FWD_ROWS, FWD_SPLIT, FWD_WAVES, FWD_KS, FWD_NKB, BWD_SPLIT, DKDV_HS, DKDV_WAVES, DKDV_QS, DQ_HS, DQ_WAVES,
  * DQ_KS, BWD_FUSED, BWD_FUSED_DELTA, BWD_FQS, BWD_FKS, BWD_FNW, BWD_CAUSAL_PART (timing tools:
  * fa2_backward_masked with a causal mask launches 1 = only dQ + Δ, 2 = only dK/dV) (see the launchers in
  * kernels/; a value that forces a plan the shape cannot take is FA2_E_INVALID at the
  * launch, never a silent fallback), and
+ * FWD_ROWS = 256 | 512: query rows per workgroup of the unsplit hand-scheduled forward (unset:
+ * 512 at D = 64 where the 512-row grid still fills the CUs, the rule at fwd_rows_auto_512 in
+ * kernels/kernel_fa2_optimized_f16.cu; O and LSE are bitwise the same either way).  512 forces
+ * the 512-row kernel on any grid size and is FA2_E_INVALID where it cannot run: D != 64,
+ * S % 64 != 0, S < 128, FWD_HS = 0, FWD_SPLIT >= 2, FWD_WAVES / FWD_KS / FWD_NKB set, or a causal
+ * mask.  256 keeps the 256-row kernel wherever the hand-scheduled forward runs.  Any other
+ * value is FA2_E_INVALID.  FWD_HS = 1 chooses the row count as the unset knob does.  And
  * the test-only HOST_SHARDS_ON_DEVICE0 = 1 (fa2_*_host run every shard on device 0,
  * so an N-way split's head offsets are testable on one GPU) and HOST_CHUNKS (head
  * chunks of the fa2_*_host pipeline; 0 = auto).  Any other name:
